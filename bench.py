@@ -7,7 +7,19 @@ pairs (B=16, S=32, SAD, 33,188,832 exact candidates per frame), inputs
 resident in HBM before the timed region.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode auto|frames|stripe]
-                  [--config 1080p|4k|8k] [--cost sad|ssd] [--no-cpu]
+                  [--config 1080p|4k|8k] [--cost sad|ssd] [--full] [--dump-outputs DIR]
+
+A plain run sets up, ramps the clock, warms up, times the K steps and prints the
+line: `value`, `ms_per_step`, `kernel_ms` and the roofline figures derived from
+them, and the device check of the timed work.  --full adds every other leg:
+the parity of the timed step's fields (one-frame searches, the committed
+pins), single_frame, ssd_mfma, ssd_single_frame, ssim, cpu_baseline, stripe_4k
+and host_stream, each with its own --no-... switch.
+--dump-outputs DIR writes the last timed step's fields, as a caller of the
+timed search receives them, to DIR/mv.npy ([F, blocks, 2]) and DIR/cost.npy
+([F, blocks]; the SSIM score's float) in float32; the inputs are seeded, so two
+builds can be compared array for array.  Above 2 Mi blocks (8K 8x8) a fixed
+seeded sample of blocks is written, its indices in DIR/sample_index.npy.
 
 A step is a batch of --frames-per-step F frames (default 16), searched in one
 launch per rank (me_full_search_batch_device; in stripe mode the rank's F
@@ -19,8 +31,8 @@ stripes, me_search_stripes_device).
   timed region (strong scaling).  Double-buffered records.
 --mode frames (the default for N = 1, where it is the same search): each rank
   searches its own F frame pairs per step: weak scaling, no collective.
-Every line also carries `stripe_4k`: BASELINE configs[3] (4K +-64) in stripe
-mode on the same ranks, with its gather parity.
+With --full the line also carries `stripe_4k`: BASELINE configs[3] (4K +-64)
+in stripe mode on the same ranks, with its gather parity.
 For N > 1: one process per GPU over RCCL.  Under torch.distributed.run
 (WORLD_SIZE set) the ranks are the launcher's; without a launcher bench.py
 starts `torch.distributed.run --nproc-per-node N` itself as a child before
@@ -67,6 +79,13 @@ def parse():
                     help="auto: frames at N = 1, stripe at N > 1")
     ap.add_argument("--config", choices=list(CONFIGS), default="1080p")
     ap.add_argument("--cost", choices=["sad", "ssd", "ssim"], default="sad")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: the timed step's field parity (one-frame "
+                         "searches, pins), single_frame, ssd_mfma, ssd_single_frame, ssim, "
+                         "cpu_baseline, stripe_4k and host_stream (each has a --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's fields (what a caller "
+                         "of the timed search receives) to DIR/mv.npy and DIR/cost.npy (float32)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-ssd", action="store_true",
                     help="skip the SSD (matrix-core) line beside a SAD run")
@@ -562,6 +581,36 @@ def batch_fields(mv_t, cost_t, F):
     return [(mv[f], co[f]) for f in range(F)]
 
 
+def device_check_only(eng, F):
+    """The timed step's parity record of a plain run: me_device_check alone."""
+    dc = device_check(eng)
+    return {"device_check": dc, "frames": F, "ok": dc == "ok",
+            "fields": "not compared (--full: one-frame searches and the committed pins)"}
+
+
+DUMP_MAX_BLOCKS = 1 << 21  # 12 bytes per block as float32 mv + cost, 8 per sample index: 40 MiB
+
+
+def dump_outputs(path, fields, cost):
+    """--dump-outputs: the last timed step's fields ([(mv, cost)] per frame, as
+    batch_fields / StripeRun.last_fields return them) as float32 arrays
+    path/mv.npy [F, nb, 2] and path/cost.npy [F, nb].  SAD and SSD costs are
+    integers below 2^24 (255^2 x 256), exact in float32; the SSIM cost is the
+    score's float bits.  Above DUMP_MAX_BLOCKS blocks in all, a fixed seeded
+    sample of the flattened blocks is written instead ([n, 2] and [n]) with its
+    sorted indices in path/sample_index.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    mv = np.stack([np.asarray(m).reshape(-1, 2) for m, _ in fields]).astype(np.float32)
+    co = np.stack([np.ascontiguousarray(c).reshape(-1) for _, c in fields])
+    co = co.view(np.float32) if cost == "ssim" else co.view(np.uint32).astype(np.float32)
+    if co.size > DUMP_MAX_BLOCKS:
+        idx = np.sort(np.random.default_rng(0).choice(co.size, DUMP_MAX_BLOCKS, replace=False))
+        mv, co = mv.reshape(-1, 2)[idx], co.reshape(-1)[idx]
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "mv.npy"), mv)
+    np.save(os.path.join(path, "cost.npy"), co)
+
+
 def verify_fields(eng, fields, ref_t, cur_t, w, h, blk, span, cost, pins, dev, singles=True):
     """Parity of a timed step's fields (frame f of the batch = ref_t[f], cur_t[f]):
     me_device_check clean; each frame equal to a one-frame-per-call search
@@ -728,10 +777,18 @@ class StripeRun:
     def gathered_fields(self):
         """A last, synchronous step; rank 0 returns [(mv, cost)] per frame."""
         import torch
-        from motionestimation_amd import shard
         k = self.step()
         self.drain()
         torch.cuda.synchronize()
+        return self.fields_of(k)
+
+    def last_fields(self):
+        """The fields of the last step run, once it has drained (rank 0)."""
+        return self.fields_of((self.i - 1) & 1)
+
+    def fields_of(self, k):
+        """Record buffer k of a drained step; rank 0 returns [(mv, cost)] per frame."""
+        from motionestimation_amd import shard
         if self.rank != 0:
             return None
         recs = [self.recs[k].cpu()] if self.world == 1 and not self.lib else self.bufs[k]
@@ -999,6 +1056,9 @@ def main():
         raise SystemExit("--gpus must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
+    if not args.full:  # a plain run: the headline leg alone
+        args.no_single = args.no_ssd = args.no_ssim = args.no_cpu = True
+        args.no_4k = args.no_stream = True
     # stdout carries exactly the one JSON line: anything else written to fd 1
     # (RCCL's version banner at communicator init, library messages) goes to stderr
     sys.stdout.flush()
@@ -1074,11 +1134,17 @@ def main():
         t_timed = time.perf_counter()
         elapsed, kern_ms = timed(step, args.steps, args.warmup, world, ramp_ms=args.ramp_ms)
         t_verify = time.perf_counter()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, batch_fields(mv_t, cost_t, F), args.cost)
         # The timed step's own output (mv_t / cost_t hold the last step's
-        # fields): device check, one-frame-per-call searches, and the pins of
-        # this batch (rank 0: its frames are the pinned batch_frames).
-        parity = verify_fields(eng, batch_fields(mv_t, cost_t, F), ref_t, cur_t, w, h, blk, span,
-                               args.cost, pins if rank == 0 else [], dev)
+        # fields): device check and, with --full, one-frame-per-call searches
+        # and the pins of this batch (rank 0: its frames are the pinned
+        # batch_frames).
+        if args.full:
+            parity = verify_fields(eng, batch_fields(mv_t, cost_t, F), ref_t, cur_t, w, h, blk,
+                                   span, args.cost, pins if rank == 0 else [], dev)
+        else:
+            parity = device_check_only(eng, F)
         parity["ok"] = all_ranks_ok(parity["ok"], world)
         t_done = time.perf_counter()
     else:
@@ -1091,7 +1157,15 @@ def main():
         elapsed, kern_ms = timed(sr.step, args.steps, args.warmup, world, ramp_ms=args.ramp_ms,
                                  drain=sr.drain)
         t_verify = time.perf_counter()
-        parity = stripe_parity(eng, sr, frames, dev, pins)
+        if args.dump_outputs:
+            fields = sr.last_fields()  # rank 0: the last timed step's gathered records
+            if rank == 0:
+                dump_outputs(args.dump_outputs, fields, args.cost)
+        if args.full:
+            parity = stripe_parity(eng, sr, frames, dev, pins)
+        else:
+            parity = device_check_only(eng, F)
+            parity["ok"] = all_ranks_ok(parity["ok"], world)
         t_done = time.perf_counter()
 
     value = units_per_step * args.steps / elapsed
@@ -1130,6 +1204,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": elapsed / args.steps * 1e3,
         "clock_ramp_ms": args.ramp_ms,
         "higher_is_better": True,
@@ -1208,7 +1283,8 @@ def main():
         wall[name] = time.perf_counter() - t0
         print(f"bench.py: leg {name}: {wall[name]:.2f} s", file=sys.stderr, flush=True)
     if mode == "stripe":
-        line["stripe_gather_parity"] = parity.get("batched_equal") == F if rank == 0 else None
+        line["stripe_gather_parity"] = (parity.get("batched_equal") == F
+                                        if rank == 0 and args.full else None)
         line["config"]["gather"] = sr.gather_impl()
     if rank == 0 and world == 1 and mode == "frames" and F > 1 and not args.no_single:
         # the same search one frame per launch (me_full_search_device), for

@@ -77,6 +77,36 @@ def test_frames_per_launch_pricing():
     assert bench.ssd_frames_per_launch(7680, 4320, 8, 128, 16) == 1
 
 
+def test_dump_outputs_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: float32 [F, nb, 2] / [F, nb] with exact integer costs and
+    the SSIM score's float; past DUMP_MAX_BLOCKS the same seeded sample of the
+    flattened blocks every time, with its indices."""
+    sys.path.insert(0, REPO)
+    import bench
+    rng = np.random.default_rng(5)
+    F, nb = 3, 50
+    mv = rng.integers(-32, 33, (F, nb, 2)).astype(np.int16)
+    co = rng.integers(0, 255 * 255 * 256 + 1, (F, nb)).astype(np.uint32)
+    fields = [(mv[f], co[f]) for f in range(F)]
+    bench.dump_outputs(str(tmp_path / "a"), fields, "ssd")
+    a_mv, a_co = np.load(tmp_path / "a" / "mv.npy"), np.load(tmp_path / "a" / "cost.npy")
+    assert a_mv.dtype == a_co.dtype == np.float32
+    assert np.array_equal(a_mv, mv) and np.array_equal(a_co.astype(np.uint32), co)
+    score = rng.random((F, nb), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "s"), [(mv[f], score[f].view(np.uint32)) for f in range(F)],
+                       "ssim")
+    assert np.array_equal(np.load(tmp_path / "s" / "cost.npy"), score)
+    monkeypatch.setattr(bench, "DUMP_MAX_BLOCKS", 40)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), fields, "ssd")
+    idx = np.load(tmp_path / "b" / "sample_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "sample_index.npy"))
+    i = idx.astype(np.int64)
+    assert len(i) == 40 and np.all(np.diff(i) > 0) and i[-1] < F * nb
+    assert np.array_equal(np.load(tmp_path / "b" / "mv.npy"), mv.reshape(-1, 2)[i])
+    assert np.array_equal(np.load(tmp_path / "b" / "cost.npy").astype(np.uint32), co.reshape(-1)[i])
+
+
 def test_committed_pmc_summary_feeds_the_roofline_figures():
     """bench.py reads its `traffic` and the 8x8 SSD line's `valu` figure from
     the committed profiles/pmc_summary.json (tools/profile.sh): the entries the

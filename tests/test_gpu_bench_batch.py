@@ -63,6 +63,41 @@ def test_headline_batch_1080p_sad_equals_oracle_every_frame(engine):
         assert _hash(mv, co, 1920, 1080, 16, "sad") == pins[f], f"frame {f} pin"
 
 
+def test_plain_run_is_the_headline_leg_and_dumps_the_pinned_fields(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one JSON line
+    with the headline figures and no other leg; --dump-outputs writes the last
+    timed step's fields, which are the pinned ones of the 16-frame batch."""
+    import json
+    import subprocess
+    import sys
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(O.REPO, "bench.py"), "--gpus", "1", "--steps",
+                        "3", "--warmup", "1", "--ramp-ms", "5", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["metric"] == bench.METRIC and d["unit"] == "candidates/s" and d["dtype"] == "u8"
+    assert d["higher_is_better"] is True and d["steps"] == 3 and d["warmup"] == 1
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    cands = d["config"]["candidates_per_frame"] * F
+    assert d["value"] == pytest.approx(cands / (d["ms_per_step"] / 1e3), rel=1e-9)
+    assert d["parity"] is True and list(d["parity_legs"]) == ["timed_step"]
+    assert d["cpu_baseline"] is None
+    for leg in ("single_frame", "ssd_mfma", "ssd_single_frame", "ssim", "stripe_4k", "host_stream"):
+        assert leg not in d, leg
+    assert sorted(p.name for p in out.iterdir()) == ["cost.npy", "mv.npy"]
+    mv, co = np.load(out / "mv.npy"), np.load(out / "cost.npy")
+    nb = d["config"]["blocks_per_frame"]
+    assert mv.dtype == co.dtype == np.float32 and mv.shape == (F, nb, 2) and co.shape == (F, nb)
+    pins = bench.load_pins("1080p", 16, 32, "sad")
+    assert len(pins) == F
+    for f in range(F):
+        assert _hash(mv[f].astype(np.int16), co[f].astype(np.uint32), 1920, 1080, 16,
+                     "sad") == pins[f], f"frame {f} pin"
+
+
 @pytest.mark.parametrize("path,kernel", [("auto", "mfma_bandwalk"), ("lean", "mfma_bandwalk"),
                                          ("prepass", "mfma_prepass")])
 def test_ssd_leg_batch_1080p_equals_reference_every_frame(engine, path, kernel):

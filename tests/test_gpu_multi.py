@@ -153,7 +153,8 @@ def _bench_ranks(nproc, backend, extra=()):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            f"--nproc-per-node={nproc}", "--master-addr=127.0.0.1", "--master-port=29731",
            os.path.join(O.REPO, "bench.py"), "--gpus", str(nproc), "--dist-backend", backend,
-           "--steps", "4", "--warmup", "1", "--no-cpu", "--no-ssd", "--no-stream", *extra]
+           "--steps", "4", "--warmup", "1", "--full", "--no-cpu", "--no-ssd", "--no-stream",
+           *extra]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -166,8 +167,8 @@ def _bench_no_launcher(nproc, backend, extra=()):
     """bench.py --gpus N with no torch.distributed.run around it (the driver's
     own command line): bench.py starts the N ranks itself."""
     cmd = [sys.executable, os.path.join(O.REPO, "bench.py"), "--gpus", str(nproc),
-           "--dist-backend", backend, "--steps", "4", "--warmup", "1", "--no-cpu", "--no-ssd",
-           "--no-stream", *extra]
+           "--dist-backend", backend, "--steps", "4", "--warmup", "1", "--full", "--no-cpu",
+           "--no-ssd", "--no-stream", *extra]
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
@@ -261,8 +262,8 @@ def test_rccl_rank_stream_budget():
     runtime's API log of the one-rank run."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", "--master-port=29733", os.path.join(O.REPO, "bench.py"),
-           "--gpus", "1", "--mode", "stripe", "--steps", "3", "--warmup", "1", "--no-cpu",
-           "--no-4k", "--ramp-ms", "5"]
+           "--gpus", "1", "--mode", "stripe", "--steps", "3", "--warmup", "1", "--full",
+           "--no-cpu", "--no-4k", "--ramp-ms", "5"]
     env = dict(os.environ, OMP_NUM_THREADS="1", AMD_LOG_LEVEL="3")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=115, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
