@@ -99,7 +99,9 @@ const char* me_version(void);
  *     GPU's CUs by themselves (e.g. 16 1080p frames per batched call);
  *     otherwise (single frames, small batches, larger ranges) the prepass +
  *     block-major pair.
- *   ME_PATH_VALU: VALU kernels only.
+ *   ME_PATH_VALU: VALU kernels only, SSIM included (every SSIM block on the
+ *     float-chain kernels; the other paths run 16x16 SSIM with S <= 64 on the
+ *     matrix cores).
  *   ME_PATH_MFMA_TILES: 16x16 SSD on the 4x4-block-tile MFMA kernel (the
  *     fallback for rows that are not 16-byte aligned).
  *   ME_PATH_MFMA_LEAN: 16x16 SSD with S <= 64 on the band-walk kernel for
@@ -133,7 +135,8 @@ me_status me_ctx_set_kernel_path(me_ctx* ctx, int path);
  * (any context, any thread -- me_ctx_last_search_path is the per-context one;
  * diagnostics and tests, e.g. that the AUTO path of
  * a 16x16 SSD search is the band-walk kernel).  The matrix-core SSD kernels
- * report the kernel of the frame's full-height block rows. */
+ * report the kernel of the frame's full-height block rows; an SSIM search
+ * reports whether the matrix-core kernel took its full-width blocks. */
 typedef enum {
   ME_SEARCH_PATH_NONE = 0,           /* no search launched yet */
   ME_SEARCH_PATH_VALU = 1,           /* SAD and SSD VALU kernels (flow, item, generic) */
@@ -142,7 +145,9 @@ typedef enum {
   ME_SEARCH_PATH_MFMA_LEAN = 4,      /* per-workgroup S2 MFMA kernel (bmv) */
   ME_SEARCH_PATH_MFMA_TILES = 5,     /* 4x4-block-tile MFMA kernel */
   ME_SEARCH_PATH_MFMA_8X8 = 6,       /* 8x8-block MFMA kernel */
-  ME_SEARCH_PATH_SSIM = 7            /* SSIM kernels */
+  ME_SEARCH_PATH_SSIM = 7,           /* SSIM float-chain kernels */
+  ME_SEARCH_PATH_SSIM_MFMA = 8       /* SSIM: the launch's full-width 16x16 blocks on the
+                                        matrix-core kernel (S <= 64) */
 } me_search_path;
 int me_last_search_path(void);
 /* The kernel family (me_search_path) of the most recent search launched by

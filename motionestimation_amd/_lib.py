@@ -22,6 +22,7 @@ ME_YUV_LUMA, ME_YUV_I420 = 0, 1
 ME_COST_SSD, ME_COST_SAD, ME_COST_SSIM = 0, 1, 2
 ME_PATH_AUTO, ME_PATH_VALU, ME_PATH_MFMA_TILES, ME_PATH_MFMA_LEAN, ME_PATH_MFMA_PREPASS = 0, 1, 2, 3, 4
 ME_PATH_PROCESS = -1
+ME_SEARCH_PATH_SSIM, ME_SEARCH_PATH_SSIM_MFMA = 7, 8  # float-chain / matrix-core SSIM kernels
 ME_MAX_BLOCK, ME_MAX_RANGE = 64, 1024
 
 # Every symbol include/me.h declares, with (restype, argtypes).

@@ -139,10 +139,10 @@ __device__ __forceinline__ f2v div_rn2(f2v a, f2v b) {
 // Statistics plane: entry (rr, x) = (mean, stddev) of the B x B ref patch at
 // frame row ylo + rr, column x (x in [0, W - B]), for every position a full
 // block of block rows [block_row_begin, block_row_end) can meet.
-// 16 x 16 blocks with S <= 64 (the matrix-core kernel reads the plane) store
-// it compact: stddev as float [rows][ld], then the patch byte sum S1r as u16
-// [rows][ld] (the mean is S1r / N, exact for N = 256, and fl(S1r / N)
-// otherwise), ld a multiple of 64 entries: a lane's four adjacent candidates
+// 16 x 16 blocks with S <= 64 off ME_PATH_VALU (the matrix-core kernel reads
+// the plane: ssim_on_mfma) store it compact: stddev as float [rows][ld],
+// then the patch byte sum S1r as u16 [rows][ld] (the mean is S1r / N, exact
+// for N = 256, and fl(S1r / N) otherwise), ld a multiple of 64 entries: a lane's four adjacent candidates
 // are one 16-byte and one 8-byte load (float2 entries took four 8-byte loads,
 // 32 tag lookups per wave each: ~49 of the kernel's 115 us at 1080p,
 // profiles/r06q_*).  Other shapes: float2 (mean, stddev) [rows][ld = pitch].
@@ -150,7 +150,16 @@ struct SsimPlane {
   int ylo, rows, pitch, ld, compact;
 };
 
-static bool ssim_compact(const SearchArgs& p) { return p.blk == 16 && p.range <= 64; }
+// The matrix-core kernel takes 16 x 16 blocks with S <= 64 unless the kernel
+// path is ME_PATH_VALU: the float kernels then run every block, with a float2
+// plane (they cannot read a compact one), no partial-row plane and no current-
+// block statistics.  attach_scratch and launch_ssim ask inside the same path
+// scope, so the scratch is sized for the planes the launch builds.
+static bool ssim_on_mfma(const SearchArgs& p) {
+  return p.blk == 16 && p.range <= 64 && !mfma_disabled();
+}
+
+static bool ssim_compact(const SearchArgs& p) { return ssim_on_mfma(p); }
 
 static bool ssim_plane(const SearchArgs& p, SsimPlane* s) {
   const int B = p.blk, S = p.range, W = p.width, H = p.height;
@@ -173,7 +182,7 @@ static bool ssim_plane(const SearchArgs& p, SsimPlane* s) {
 // matrix-core SSIM kernel runs that row too.
 static bool ssim_hb_plane(const SearchArgs& p, SsimPlane* s, int* hbh) {
   const int S = p.range, W = p.width, H = p.height;
-  if (p.blk != 16 || S > 64 || W < 16 || H < 16 || H % 16 == 0) return false;
+  if (!ssim_on_mfma(p) || W < 16 || H < 16 || H % 16 == 0) return false;
   const int hb_row = H / 16;
   if (hb_row < p.block_row_begin || hb_row >= p.block_row_end) return false;
   *hbh = H - 16 * hb_row;
@@ -192,7 +201,7 @@ static size_t ssim_plane_bytes(const SsimPlane& s) {
 // 16 x 16 blocks on the matrix cores: (mean, stddev, byte sum) of each
 // full-width current block of the launch's rows
 static size_t ssim_cur_stats_bytes(const SearchArgs& p) {
-  if (p.blk != 16 || p.range > 64 || p.width < 16) return 0;
+  if (!ssim_on_mfma(p) || p.width < 16) return 0;
   return (size_t)(p.block_row_end - p.block_row_begin) * (size_t)(p.width / 16) * sizeof(float4);
 }
 
@@ -801,10 +810,15 @@ __global__ __launch_bounds__(256) void me_ssim_mfma_kernel(SearchArgs p, SsimSta
       *reinterpret_cast<lds_u32x4*>((uintptr_t)(lds_addr(win) + 16u * (uint32_t)i)) = v ^ 0x80808080u;
     }
   } else {
+    // rows the candidates need: the last candidate row's 16 patch rows, which
+    // end at tly + S + 15 < block_row_end * 16 + S -- inside the rows a stripe's
+    // caller keeps resident (include/me.h); the tiles' rows below them (R
+    // rounds ncy up to 16) belong to masked candidates only
+    const int yend = min(H, wy0 + ncy + 15);
     for (int i = tid; i < R * LP; i += 256) {
       const int rr = i / LP, col = i - rr * LP;
       const int y = wy0 + rr, x = 16 * i0 + col;
-      win[i] = (y < H && x < W) ? (uint8_t)(p.ref[(ptrdiff_t)(y - p.ref_row0) * p.stride + x] ^ 0x80) : 0;
+      win[i] = (y < yend && x < W) ? (uint8_t)(p.ref[(ptrdiff_t)(y - p.ref_row0) * p.stride + x] ^ 0x80) : 0;
     }
   }
   __syncthreads();
@@ -986,6 +1000,7 @@ hipError_t launch_ssim(const SearchArgs& p, hipStream_t stream) {
     r_full = stats ? std::max(0, std::min(p.block_row_end, p.height / 16) - p.block_row_begin) : 0;
     const int a16 = p.stride % 16 == 0 && (uintptr_t)p.ref % 16 == 0 && p.ref_bytes > 0;
     const int nrow = r_full + (hb_mfma ? 1 : 0);
+    note_path(8);
     hipLaunchKernelGGL(me_ssim_mfma_kernel, dim3((unsigned)(nrow * J.nbxf)), dim3(256),
                        ssim_mfma_lds(p.range), stream, p, J, a16);
   }

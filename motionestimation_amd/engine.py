@@ -51,8 +51,9 @@ def set_kernel_path(path: str) -> None:
     """'auto': 16x16 and 8x8 SSD on the matrix cores (i8 MFMA; 16x16 with
     S <= 64 on the band-walk kernel when a launch's strips fill the CUs, else
     the prepass + block-major pair), the rest on the VALU kernels; 'valu':
-    VALU kernels only; 'tiles': as 'auto' with 16x16 SSD on the 4x4-block-tile
-    MFMA kernel; 'lean': 16x16 SSD (S <= 64) on the band-walk kernel for every
+    VALU kernels only (SSIM too: its float-chain kernels, where the other
+    paths run 16x16 SSIM with S <= 64 on the matrix cores); 'tiles': as 'auto'
+    with 16x16 SSD on the 4x4-block-tile MFMA kernel; 'lean': 16x16 SSD (S <= 64) on the band-walk kernel for every
     launch (no prepass planes, no scratch); 'prepass': 16x16 SSD on the S2
     prepass + block-major pair.  Process-wide; results are identical."""
     if path not in _PATH_CODES:
@@ -61,7 +62,8 @@ def set_kernel_path(path: str) -> None:
 
 
 SEARCH_PATHS = {0: "none", 1: "valu", 2: "mfma_prepass", 3: "mfma_bandwalk", 4: "mfma_lean",
-                5: "mfma_tiles", 6: "mfma_8x8", 7: "ssim"}
+                5: "mfma_tiles", 6: "mfma_8x8", _lib.ME_SEARCH_PATH_SSIM: "ssim",
+                _lib.ME_SEARCH_PATH_SSIM_MFMA: "ssim_mfma"}
 
 
 def last_search_path() -> str:
@@ -408,13 +410,12 @@ class Graph:
         set_kernel_path()'s names, or None to follow the process-wide path."""
         if path is not None and path not in _PATH_CODES:
             raise MEError(_lib.ME_EINVAL, f"unknown kernel path {path!r}")
-        code = _lib.ME_PATH_PROCESS if path is None else _PATH_CODES[path]
-        check(_lib.lib().me_ctx_set_kernel_path(self._h, code), self._h)
+        self._eng.set_kernel_path(path)  # the handle here is the graph's, not the context's
 
     def last_search_path(self, device_index: int = 0) -> str:
         """The kernel family of this context's latest search on its device
         `device_index` (me_ctx_last_search_path)."""
-        return SEARCH_PATHS.get(_lib.lib().me_ctx_last_search_path(self._h, device_index), "unknown")
+        return self._eng.last_search_path(device_index)
 
     def close(self) -> None:
         if getattr(self, "_h", None):

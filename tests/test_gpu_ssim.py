@@ -34,7 +34,18 @@ def test_ssim_reference_goldens(engine, manifest):
 
 @pytest.mark.parametrize("blk,span,shape", [(16, 5, (75, 100)), (8, 9, (64, 72)),
                                             (32, 3, (96, 96)), (4, 6, (30, 41)),
-                                            (16, 120, (150, 160))])
+                                            (16, 120, (150, 160)),
+                                            # 16 x 16 past the matrix-core kernel's S <= 64: the
+                                            # float kernel's register-row path with a float2
+                                            # statistics plane, while the window fits in LDS:
+                                            # 256 + (16 + 2 S)^2 + SSIM_PAD (11) <=
+                                            # GENERIC_LDS_BUDGET (61440) holds up to S = 115
+                                            # (60783) and fails at 116 (61771: global reads)
+                                            (16, 65, (100, 136)), (16, 96, (150, 176)),
+                                            (16, 115, (96, 112)), (16, 116, (96, 112)),
+                                            # larger spans on the other block sizes
+                                            (8, 60, (80, 96)), (12, 40, (75, 100)),
+                                            (24, 30, (90, 120))])
 def test_ssim_vs_oracle_shapes(engine, blk, span, shape):
     """Partial blocks, w*h > 256 (float chains that round), and a window too
     large for LDS (S = 120: read from global memory)."""
