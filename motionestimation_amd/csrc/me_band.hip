@@ -890,17 +890,6 @@ __global__ __launch_bounds__(64 * (NSW + PW), 4) void me_mfma_bw_kernel(SearchAr
 #endif
 }
 
-static int bw_cu_count() {
-  static const int cus = []() {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-      n = 256;
-    return n;
-  }();
-  return cus;
-}
-
 // Smallest pitch >= need with pitch = r (mod m): the conflict-free classes of
 // the tiles' ds_read_b128 lane groups (window LP = 32 mod 64 bytes, P0 PP = 8
 // mod 16 ints; checked for every group of 16 lanes).
@@ -954,7 +943,7 @@ bool plan_bw(const SearchArgs& p, MfmaGeom* g, int jobs) {
   // shorter middle ones, 12 bands worst instead of 13 at 1080p one frame,
   // 1.5 % slower again: 38.6 against 38.0 us per call, r06zl_bw_seg.jsonl.
   // The segments' band counts do not set the time alone.)
-  const int cus = bw_cu_count() * wgs_cu;
+  const int cus = cu_count() * wgs_cu;
   const int nfull = g->row0 + rows;  // (rows from row0: the job's full-height rows)
   auto lo_b = [&](int br) { return std::max(16 * br - S, 0) >> 4; };
   auto hi_b = [&](int br) { return std::min(16 * br + S, p.height - 16) >> 4; };
@@ -984,7 +973,7 @@ bool plan_bw(const SearchArgs& p, MfmaGeom* g, int jobs) {
   g->bw_segs = best_segs;
   // Launches of whole rounds of strips take the per-XCD tail split instead.
   g->bw_xt = 0;
-  g->bw_cx = bw_cu_count() / 8;
+  g->bw_cx = cu_count() / 8;
   if (tuning().bw_xt != 0 && tuning().bw_seg == 0 && per >= cus && g->bw_cx > 0) {
     g->bw_xt = 1;
     g->bw_seg_rows = rows;
@@ -1010,7 +999,7 @@ bool plan_bw(const SearchArgs& p, MfmaGeom* g, int jobs) {
 }
 
 bool bw_one_round(const MfmaGeom& g, int jobs) {
-  return (long)std::max(jobs, 1) * g.bw_strips * g.bw_segs <= (long)bw_cu_count();
+  return (long)std::max(jobs, 1) * g.bw_strips * g.bw_segs <= (long)cu_count();
 }
 
 hipError_t launch_bw(const SearchArgs& p, const MfmaGeom& g0, const MfmaJobs& jb0, hipStream_t stream) {

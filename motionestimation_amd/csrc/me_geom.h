@@ -1,0 +1,158 @@
+// me_geom.h -- search geometry shared by the kernels and the host-only
+// planners (internal to libme_hip.so).  Plain structs and integer helpers:
+// nothing here needs HIP, so me_valu_plan.cpp and the CPU harnesses
+// (oracle/plan_dump.cc, oracle/san_main.cc) include it as it stands.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace me {
+
+enum { COST_SSD = 0, COST_SAD = 1, COST_SSIM = 2 };
+
+constexpr int GENERIC_THREADS = 256;
+constexpr int GENERIC_LDS_BUDGET = 60 * 1024;
+constexpr int QSAD_LDS_BUDGET = 40 * 1024;  // 4 workgroups per CU (160 KB LDS)
+constexpr int FLOW_LDS_BUDGET = 160 * 1024;  // the flow kernel: one workgroup per CU
+
+// One search launch: block rows [block_row_begin, block_row_end) of a
+// width x height frame.  ref / cur point at frame rows ref_row0 / cur_row0.
+// Outputs are indexed (block row - block_row_begin) * nbx + block column.
+struct SearchArgs {
+  const uint8_t* ref;
+  const uint8_t* cur;
+  int ref_row0, cur_row0;
+  int width, height, stride;
+  int blk, range;
+  int nbx;
+  int block_row_begin, block_row_end;
+  int cost_kind;
+  int16_t* mv;
+  uint32_t* cost;
+  uint32_t ref_bytes;  // readable bytes from ref (buffer range check), and from cur
+  uint32_t cur_bytes;
+  uint32_t* sched;     // SCHED_WORDS u32 (me_kernels.h), zeroed between launches; or null
+  uint8_t* scratch;    // device scratch of the MFMA SSD path (mfma_ssd_scratch bytes) or null
+  size_t scratch_bytes;
+  // MFMA SSD cross-workgroup merge (self-resetting): 16 keys (~0) per tile and
+  // one arrival counter (0) per tile, merge_tiles tiles; or null
+  unsigned long long* mkeys;
+  uint32_t* mcnt;
+  size_t merge_tiles;
+};
+
+// Bytes the kernels may read from a plane that holds frame rows from row0 on,
+// for a search of block rows up to r1 (the DMA descriptors' range): the rows
+// the stripe contract guarantees resident (include/me.h).  The ref plane's
+// rows end S past the last block row, both at the frame's height.
+inline uint32_t resident_bytes(int rows_end, int row0, int stride, int width) {
+  const long rows = rows_end - row0;
+  return rows > 0 ? (uint32_t)((rows - 1) * (long)stride + width) : 0;
+}
+inline uint32_t ref_resident_bytes(int r1, int blk, int range, int height, int row0, int stride,
+                                   int width) {
+  const int end = r1 * blk + range < height ? r1 * blk + range : height;
+  return resident_bytes(end, row0, stride, width);
+}
+inline uint32_t cur_resident_bytes(int r1, int blk, int height, int row0, int stride, int width) {
+  const int end = r1 * blk < height ? r1 * blk : height;
+  return resident_bytes(end, row0, stride, width);
+}
+
+struct QsadGeom {
+  int tb;          // blocks per workgroup
+  int rows_alloc;  // LDS tile rows (chunks*K + B - 1)
+  int row0;        // first block row of the launch
+  int nrows;       // block rows in the launch
+  int groups;      // 4-wide dx groups per block
+  int chunks;      // K-row dy chunks
+  int cpp;         // dy chunks per LDS pass
+  int pitch;       // bytes per LDS tile row (multiple of 16)
+  int tile_bytes;  // rows_alloc * pitch
+  uint32_t pitch_magic;  // umulhi(d, pitch_magic) == d / pitch on the staged range
+  uint32_t magic_groups; // umulhi(t, magic_groups) == t / groups on an item's tasks
+  int threads;     // workgroup size
+  int lds;         // dynamic LDS bytes
+  int wg_per_row;  // workgroups per block row
+  uint32_t magic_wpr;  // umulhi(t, magic_wpr) == t / wg_per_row for every tile index of
+                       // the planned rows (host-checked; 0: divide)
+  uint32_t magic_tb;   // 0xFFFFFFFF / tb + 1: an item's / nb magic when nb == tb > 1
+  int strip_w;     // > 0: tiles run in vertical strips of strip_w tile columns, each
+                   // strip top to bottom (wide frames: an XCD's L2 keeps the strip's
+                   // window rows while the tile rows that read them pass)
+  int nbx_full;    // full-width blocks per row
+  int aligned;     // 4-byte aligned global rows
+  int tile16;      // ref tile staged in 16-byte granules (X0, width, rows 16-byte aligned)
+  int fold;        // SAD, S % 4 == 0: groups = S/2 cover dx in [-S, S-1]; the dx = +S
+                   // column is spread over lanes gi < K, one v_sad_u8 candidate each
+  int dyn_tiles;   // dynamic tile pulls when tiles >= dyn_tiles * workgroups (0: never)
+  int pull_ahead;  // dynamic: tile ti + pull_ahead is claimed when tile ti starts (1 or 2)
+  int flow_slots;  // me_flow_kernel: LDS ring slots (0: the persistent item kernel)
+  int prio;        // waves issuing staging raise their issue priority (s_setprio) meanwhile
+  int fair;        // me_flow_kernel: lo | hi << 8 | mode << 16 (0: off): a wave whose
+                   // wave-task others have overtaken by >= lo / hi pulls raises its
+                   // issue priority to 1 / 2 (checked every 4 rows; 8 / 16 by
+                   // default) in launches with slot refills (mode 1)
+};
+
+// A search job: block rows [r0, r1) of one frame (or row stripe), its planes
+// (ref / cur hold frame rows from ref_row0 / cur_row0, as in SearchArgs) and
+// its records (indexed from r0).  Jobs of one launch share the frame geometry.
+struct SearchJob {
+  const uint8_t* ref;
+  int ref_row0;
+  const uint8_t* cur;
+  int cur_row0;
+  int r0, r1;
+  int16_t* mv;
+  uint32_t* cost;
+};
+
+// The flow kernel's job table (kernel argument): job j owns launch tiles
+// [tile_pre[j], tile_pre[j + 1]).  A batch of frames or stripes (the per-rank
+// step of a multi-GPU split) fills the GPU in one launch.
+constexpr int MAX_JOBS = 32;
+struct FlowJobs {
+  int n;
+  int tile_pre[MAX_JOBS + 1];
+  int r0[MAX_JOBS];
+  int ref_row0[MAX_JOBS], cur_row0[MAX_JOBS];
+  uint32_t ref_bytes[MAX_JOBS], cur_bytes[MAX_JOBS];
+  const uint8_t* ref[MAX_JOBS];
+  const uint8_t* cur[MAX_JOBS];
+  int16_t* mv[MAX_JOBS];
+  uint32_t* cost[MAX_JOBS];
+};
+
+// ---- the VALU kernels' planners (me_valu_plan.cpp: host-only, pure) ----
+
+// Alignment class of a search's planes: bit 0 = stride, ref and cur 4-byte
+// aligned; bit 1 = stride and ref 16-byte aligned; bit 2 = cur 16-byte aligned.
+enum { ALIGN_4 = 1, ALIGN_REF16 = 2, ALIGN_CUR16 = 4, ALIGN_ALL = 7 };
+inline int align_class(int stride, const void* ref, const void* cur) {
+  const uintptr_t r = (uintptr_t)ref, c = (uintptr_t)cur;
+  return (stride % 4 == 0 && r % 4 == 0 && c % 4 == 0 ? ALIGN_4 : 0) |
+         (stride % 16 == 0 && r % 16 == 0 ? ALIGN_REF16 : 0) | (c % 16 == 0 ? ALIGN_CUR16 : 0);
+}
+
+// What a plan depends on (and the plan cache's key): the frame, the search,
+// the block rows planned for (every job's rows of a batched launch) and the
+// alignment class of the planes.
+struct PlanShape {
+  int width, height, stride, blk, range, cost, rows, align;
+  bool operator==(const PlanShape& o) const {
+    return width == o.width && height == o.height && stride == o.stride && blk == o.blk &&
+           range == o.range && cost == o.cost && rows == o.rows && align == o.align;
+  }
+};
+
+struct Tuning;  // me_tuning.h
+
+// The item kernel's plan (me_fast_kernel<cost, B, *k_out>) for s on a device
+// of `cus` CUs; false: the shape goes to the generic kernel.  g->row0 and
+// g->nrows stay 0 (the job table carries the rows).
+bool plan_fast(const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g, int* k_out);
+// The flow kernel's plan (me_flow_kernel<16, 13>); false: the item kernel's turn.
+bool plan_flow(const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g);
+
+}  // namespace me

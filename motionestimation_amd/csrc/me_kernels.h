@@ -4,13 +4,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "me_geom.h"
+
 namespace me {
 
-enum { COST_SSD = 0, COST_SAD = 1, COST_SSIM = 2 };
-
-constexpr int GENERIC_THREADS = 256;
-constexpr int GENERIC_LDS_BUDGET = 60 * 1024;
-constexpr int QSAD_LDS_BUDGET = 40 * 1024;  // 4 workgroups per CU (160 KB LDS)
 // sched holds SCHED_WORDS u32: [0, 16) the item kernel's 8 two-ended band
 // counters (u64: owner claims in the low half, thieves in the high half),
 // [SCHED_ARRIVE] its arrivals (the last workgroup out re-zeroes [0, 17)),
@@ -19,32 +16,6 @@ constexpr int QSAD_LDS_BUDGET = 40 * 1024;  // 4 workgroups per CU (160 KB LDS)
 constexpr int SCHED_WORDS = 32;
 constexpr int SCHED_ARRIVE = 16;
 constexpr int SCHED_ERR = 31;
-
-// One search launch: block rows [block_row_begin, block_row_end) of a
-// width x height frame.  ref / cur point at frame rows ref_row0 / cur_row0.
-// Outputs are indexed (block row - block_row_begin) * nbx + block column.
-struct SearchArgs {
-  const uint8_t* ref;
-  const uint8_t* cur;
-  int ref_row0, cur_row0;
-  int width, height, stride;
-  int blk, range;
-  int nbx;
-  int block_row_begin, block_row_end;
-  int cost_kind;
-  int16_t* mv;
-  uint32_t* cost;
-  uint32_t ref_bytes;  // readable bytes from ref (buffer range check), and from cur
-  uint32_t cur_bytes;
-  uint32_t* sched;     // SCHED_WORDS u32 (layout above), zeroed between launches; or null
-  uint8_t* scratch;    // device scratch of the MFMA SSD path (mfma_ssd_scratch bytes) or null
-  size_t scratch_bytes;
-  // MFMA SSD cross-workgroup merge (self-resetting): 16 keys (~0) per tile and
-  // one arrival counter (0) per tile, merge_tiles tiles; or null
-  unsigned long long* mkeys;
-  uint32_t* mcnt;
-  size_t merge_tiles;
-};
 
 // Write block `out`'s MV from a merged 64-bit key (cost << 32 | (dy + 32768)
 // << 16 | (dx + 32768)): one 4-byte store of the (mvx, mvy) int16 pair when the
@@ -59,71 +30,6 @@ __device__ __forceinline__ void store_mv(int16_t* mv, int out, unsigned long lon
     mv[2 * out + 1] = (int16_t)((int)((kk >> 16) & 0xFFFF) - 32768);
   }
 }
-
-struct QsadGeom {
-  int tb;          // blocks per workgroup
-  int rows_alloc;  // LDS tile rows (chunks*K + B - 1)
-  int row0;        // first block row of the launch
-  int nrows;       // block rows in the launch
-  int groups;      // 4-wide dx groups per block
-  int chunks;      // K-row dy chunks
-  int cpp;         // dy chunks per LDS pass
-  int pitch;       // bytes per LDS tile row (multiple of 16)
-  int tile_bytes;  // rows_alloc * pitch
-  uint32_t pitch_magic;  // umulhi(d, pitch_magic) == d / pitch on the staged range
-  uint32_t magic_groups; // umulhi(t, magic_groups) == t / groups on an item's tasks
-  int threads;     // workgroup size
-  int lds;         // dynamic LDS bytes
-  int wg_per_row;  // workgroups per block row
-  uint32_t magic_wpr;  // umulhi(t, magic_wpr) == t / wg_per_row for every tile index of
-                       // the planned rows (host-checked; 0: divide)
-  uint32_t magic_tb;   // 0xFFFFFFFF / tb + 1: an item's / nb magic when nb == tb
-  int strip_w;     // > 0: tiles run in vertical strips of strip_w tile columns, each
-                   // strip top to bottom (wide frames: an XCD's L2 keeps the strip's
-                   // window rows while the tile rows that read them pass)
-  int nbx_full;    // full-width blocks per row
-  int aligned;     // 4-byte aligned global rows
-  int tile16;      // ref tile staged in 16-byte granules (X0, width, rows 16-byte aligned)
-  int fold;        // SAD, S % 4 == 0: groups = S/2 cover dx in [-S, S-1]; the dx = +S
-                   // column is spread over lanes gi < K, one v_sad_u8 candidate each
-  int dyn_tiles;   // dynamic tile pulls when tiles >= dyn_tiles * workgroups (0: never)
-  int pull_ahead;  // dynamic: tile ti + pull_ahead is claimed when tile ti starts (1 or 2)
-  int flow_slots;  // me_flow_kernel: LDS ring slots (0: the persistent item kernel)
-  int prio;        // waves issuing staging raise their issue priority (s_setprio) meanwhile
-  int fair;        // me_flow_kernel: lo | hi << 8 | mode << 16 (0: off): a wave whose
-                   // wave-task others have overtaken by >= lo / hi pulls raises its
-                   // issue priority to 1 / 2 (checked every 4 rows; 8 / 16 by
-                   // default) in launches with slot refills (mode 1)
-};
-
-// A search job: block rows [r0, r1) of one frame (or row stripe), its planes
-// (ref / cur hold frame rows from ref_row0 / cur_row0, as in SearchArgs) and
-// its records (indexed from r0).  Jobs of one launch share the frame geometry.
-struct SearchJob {
-  const uint8_t* ref;
-  int ref_row0;
-  const uint8_t* cur;
-  int cur_row0;
-  int r0, r1;
-  int16_t* mv;
-  uint32_t* cost;
-};
-
-// The flow kernel's job table (kernel argument): job j owns launch tiles
-// [tile_pre[j], tile_pre[j + 1]).  A batch of frames or stripes (the per-rank
-// step of a multi-GPU split) fills the GPU in one launch.
-constexpr int MAX_JOBS = 32;
-struct FlowJobs {
-  int n;
-  int tile_pre[MAX_JOBS + 1];
-  int r0[MAX_JOBS];
-  int ref_row0[MAX_JOBS], cur_row0[MAX_JOBS];
-  uint32_t ref_bytes[MAX_JOBS], cur_bytes[MAX_JOBS];
-  const uint8_t* ref[MAX_JOBS];
-  const uint8_t* cur[MAX_JOBS];
-  int16_t* mv[MAX_JOBS];
-  uint32_t* cost[MAX_JOBS];
-};
 
 // Equal-geometry SSD searches of one matrix-core launch pair (prepass + main
 // kernel): frames of one size and the same block rows.  Job j's planes and
@@ -220,7 +126,9 @@ int last_path();
 hipError_t lds_attr(const void* fn, int lds);
 hipError_t launch_generic(const SearchArgs& p, int bx0, int nbx_range, int row0, int nrows,
                           hipStream_t stream);
-bool plan_fast(const SearchArgs& p, QsadGeom* g, int* k_out);
+// CUs of the current device (every device of a context is the same part; 256,
+// the MI355X's, when the query fails): queried once, thread-safe.
+int cu_count();
 
 // SSIM-cost search (me_ssim.hip): every block of rows [block_row_begin, block_row_end).
 hipError_t launch_ssim(const SearchArgs& p, hipStream_t stream);

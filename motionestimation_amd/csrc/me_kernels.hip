@@ -1283,356 +1283,6 @@ hipError_t launch_generic(const SearchArgs& p, int bx0, int nbx_range, int row0,
   return hipGetLastError();
 }
 
-// Plan the fast kernels.  SAD lanes own 4 dx (one qsad group), SSD lanes one
-// dx; both own K dy.  Search (fold, K, TB, chunks per pass) for the most
-// useful work per wave-task (dy padding, the masked 4th column of the last
-// SAD group or the fold's extra column, idle lanes of partly filled waves)
-// within the LDS budget; then prefer fewer passes and smaller tiles (finer
-// work items).  256 threads per workgroup: 4 workgroups of 4 waves per CU at
-// the kernels' <= 128 VGPRs.
-static int cu_count();
-
-bool plan_fast(const SearchArgs& p, QsadGeom* g, int* k_out) {
-  const int B = p.blk, S = p.range;
-  if (B != 16 && B != 8) return false;
-  if (S < 1 || S > 255) return false;
-  g->nbx_full = p.width / B;
-  if (g->nbx_full < 1) return false;
-  const bool sad = p.cost_kind == COST_SAD;
-  const int D = 2 * S + 1;
-  const int CW = B / 4;
-  // Fold needs a = 0 (S % 4 == 0) and the tail words of every block aligned
-  // for one ds_read of B bytes (b*B + 2S multiple of B: S % 8 == 0 for B = 16).
-  const bool fold_ok = sad && S % 4 == 0 && (B == 8 || S % 8 == 0);
-  // SAD rows carry an alignment word for a = (tlx - S) mod 4 <= 3; with S % 4
-  // == 0 (tlx a multiple of B) a = 0 and the lanes read exactly 4G + B bytes
-  // past the block's first tile column: no word (1080p tb = 3 rows 112 instead
-  // of 144 bytes; the 2- and 4-way stripe times moved within box-to-box
-  // noise, profiles/r02al_stripe_sweeps.jsonl)
-  const int aw = S % 4 == 0 ? 0 : 4;
-  static const int Ks[] = {26, 13, 11, 8, 5};
-  // K = 26 (8x8 SAD): twice the candidates per lane-task, so the task decode,
-  // cur loads, fold column and key merge are paid per 104 candidates, not 52
-  // (8K +-128: 18.23 -> 17.40 ms, tb 8 at the compiled pitch 336;
-  // profiles/r03ar_plan_8k.jsonl)
-  const bool k26_auto = sad && B == 8;
-  // K = 5 (a quarter-size wave-task) only for SAD searches too small to give
-  // every SIMD two K = 13 wave-tasks (an 8-way 1080p stripe: 1.25 per SIMD, so
-  // a quarter of the SIMDs ran a second round); K >= 8 otherwise.
-  bool small = false;
-  if (sad) {
-    const int G13 = S % 4 == 0 && (B == 8 || S % 8 == 0) ? S / 2 : (2 * S + 3 + 1 + 3) / 4;
-    const double lanes = (double)(p.block_row_end - p.block_row_begin) * (p.width / B) * G13 *
-                         ((D + 12) / 13);
-    small = lanes / 64.0 < 2.0 * 4 * cu_count();
-  }
-  // Tuning build override (tools/plan_sweep.py): ME_PLAN="K,tb,cpp,threads[,fold]",
-  // validated in me_api.hip; 0 = free (fold: -1 = free).
-  const Tuning& tu = tuning();
-  const int force[5] = {tu.plan_k, tu.plan_tb, tu.plan_cpp, tu.plan_threads, tu.plan_fold};
-  const int thr = force[3] > 0 ? force[3] : 256;
-  const int rows = p.block_row_end - p.block_row_begin;
-  double best = -1;
-  int bK = 13, bTB = 1, bC = 1, bF = 0, bG = 1;
-  for (int fold = 0; fold <= 1; fold++) {
-    if (fold && !fold_ok) continue;
-    if (force[4] >= 0 && fold != force[4]) continue;
-    // SAD: worst case a = 3 without fold
-    const int G = sad ? (fold ? S / 2 : (2 * S + 3 + 1 + 3) / 4) : D;
-    // useful share of a lane's candidates (the last group's padding), and the
-    // fold's extra cost per task (one B-row v_sad_u8 column + its key)
-    const double use_dx = sad ? (fold ? 1.0 : (double)D / (4.0 * G)) : 1.0;
-    for (int K : Ks) {
-      if (force[0] && K != force[0]) continue;
-      // (K = 5 is instantiated for 16x16 SAD only: other small searches keep K >= 8;
-      // K = 26 for 8x8 SAD only)
-      if (K == 5 && (!sad || B != 16)) continue;
-      if (K == 26 && (!sad || B != 8 || (!force[0] && !k26_auto))) continue;
-      if (!force[0] && (K == 5) != (small && B == 16)) continue;
-      if (fold && G < K) continue;
-      const int chunks = (D + K - 1) / K;
-      if (K == 5 && !force[0]) {
-        // small search: one block per tile, every chunk in one pass, so each
-        // block is its own workgroup item (1,020 of them in an 8-way 1080p
-        // stripe: about one quarter-size wave-task per wave, all SIMDs busy).
-        // No fold (17 groups): the fold's narrower rows measured slower here
-        // (9-row stripe 20.2 vs 19.65 us, CIF +-16 12.4 vs 11.05 us,
-        // profiles/r02am_small_plan_fold.txt).
-        const int pt0 = ((sad ? 4 * G + B + aw : 2 * S + 1 + 3 + B + 4) + 15) & ~15;
-        const int pt = ((pt0 >> 4) & 1) ? pt0 : pt0 + 16;
-        const long lds = 128 + 2 * ((long)B * B + (long)(chunks * K + B - 1) * pt);
-        if (lds <= QSAD_LDS_BUDGET && best < 0) {
-          best = 1.0; bK = K; bTB = 1; bC = chunks; bF = fold; bG = G;
-        }
-        continue;
-      }
-      const double kpad = (double)D / (chunks * K);
-      const double tail = fold ? 0.5 * (B * CW + 16) / (K * B * CW * 4 + 340) : 0.0;
-      // Waves that hold whole (block, chunk) groups (64 % G == 0 or G % 64
-      // == 0) read one cur block and share one row range per wave: measured
-      // ~5 % faster than waves straddling blocks (8K B8: G 64 vs 65).
-      const double wave_align = (64 % G == 0 || G % 64 == 0) ? 1.03 : 1.0;
-      for (int tb = 1; tb <= 16; tb++) {
-        if (force[1] && tb != force[1]) continue;
-        // One-block tiles restage a whole window per block and leave waves of
-        // every item part empty: measured slower than two-block tiles wherever
-        // both fit (1080p: 171 vs 121 us static; 4K block rows 0..17, the edge
-        // stripe of an 8-way split: 0.228 vs 0.188 ms; profiles/r02h_dyn.jsonl).
-        if (tb == 1 && !force[1] && g->nbx_full >= 2) continue;
-        // bytes the lanes touch per row (+ a <= 3, + alignment word)
-        const int width = (tb - 1) * B + (sad ? 4 * G + B + aw : 2 * S + 1 + 3 + B + 4);
-        int pt = (width + 15) & ~15;
-        if (((pt >> 4) & 1) == 0) pt += 16;
-        for (int cpp = chunks; cpp >= 1; cpp--) {
-          if (force[2] && cpp != force[2]) continue;
-          const long lds = 128 + 2 * ((long)tb * B * B + (long)(cpp * K + B - 1) * pt);
-          if (lds > QSAD_LDS_BUDGET) continue;
-          int passes = 0;
-          for (int c0 = 0; c0 < chunks; c0 += cpp) passes++;
-          const long items = (long)((g->nbx_full + tb - 1) / tb) * rows * passes;
-          // Cost of an item in wave-tasks: its waves (a partly filled wave
-          // costs a whole one), for SAD half of the wave slots its last round of
-          // `thr` lanes leaves idle (the CU's other workgroups take up the
-          // rest: 4K +-64, 68 block rows, tb 5 = 10 waves in rounds of 4:
-          // 0.637 ms against tb 8's 0.570, profiles/r02aa_plan_sweep_4k_68rows.jsonl),
-          // + ~0.45 for staging, barrier and output (fitted on
-          // tools/plan_sweep.py runs).  With few items per workgroup (< 8 of
-          // 1024) a partial last round is not amortised at all: whole rounds.
-          const bool many = items >= 8L * 1024;
-          double cost = 0, useful = 0;
-          for (int c0 = 0; c0 < chunks; c0 += cpp) {
-            const int t = tb * G * (chunks - c0 < cpp ? chunks - c0 : cpp);
-            const int rounds = (t + thr - 1) / thr;
-            const int waves = (t + 63) / 64, idle = rounds * (thr / 64) - waves;
-            // few items: every extra round lengthens the kernel's tail too
-            cost += (many ? waves + (sad ? 0.5 * idle : 0.0) : rounds * (thr / 64) + 0.5 * (rounds - 1)) + 0.45;
-            useful += t / 64.0;
-          }
-          // Workgroups take whole tiles (every pass of a tile runs on the
-          // workgroup holding its keys): too few tiles leave workgroup slots
-          // idle (and nothing to prefetch): aim for >= 2 tiles per resident
-          // workgroup (4 per CU).
-          const long tiles = items / passes;
-          const double fill = tiles >= 2048 ? 1.0 : (double)tiles / 2048;
-          // K = 13 measured best wherever it fits (more candidates per row load
-          // and per epilogue than the padding it costs).
-          // K = 26 over K = 13 where it fits (8x8 SAD), at the compiled tile
-          // pitch 336 if a tb gives it (tb 8: 17.40 ms; tb 12 / 16 at runtime
-          // pitches 17.68 / 17.64 ms)
-          const double kpref = K == 26 ? (pt == 336 ? 1.05 : 1.03) : K == 13 ? 1.0 : 0.95;
-          // the last tile of a block row holds nbx_full % tb blocks
-          const double tile_fill =
-              (double)g->nbx_full / ((double)((g->nbx_full + tb - 1) / tb) * tb);
-          const double score = kpad * kpref * wave_align * tile_fill * use_dx / (1.0 + tail) * useful / cost *
-                               (0.7 + 0.3 * fill) - 0.002 * tb;
-          if (score > best + 1e-9) {
-            best = score; bK = K; bTB = tb; bC = cpp; bF = fold; bG = G;
-          }
-        }
-      }
-    }
-  }
-  if (best < 0) return false;  // nothing fits (only with an ME_PLAN override)
-  g->fold = bF;
-  g->groups = bG;
-  // Dynamic tile pulls from this many tiles per workgroup on (ME_DYN overrides
-  // in the tuning build; 0 = static bands only).
-  {
-    const int dyn_env = tu.dyn;
-    // 3: measured (tools/dyn_sweep.sh) -- 4K (3.96 tiles/WG) and 8K gain
-    // (8K -11 % with stealing), 1080p (2.7 tiles/WG) loses: its workgroups
-    // start items in lockstep and the item-start pulls serialise on the
-    // device-scope counters while wave 0 waits.
-    g->dyn_tiles = dyn_env >= 0 ? dyn_env : 3;
-    // ... and only for tiles of >= 16 wave-tasks: small tiles pay the pull per
-    // few tasks (1080p tb = 2: 184 vs 121 us static; profiles/r02h_dyn.jsonl).
-    const long tile_lanes = (long)bTB * bG * ((D + bK - 1) / bK);
-    if (dyn_env < 0 && tile_lanes < 16L * 64) g->dyn_tiles = 0;
-  }
-  g->tb = bTB;
-  g->cpp = bC;
-  g->chunks = (D + bK - 1) / bK;
-  // recompute the pitch of the chosen tb
-  {
-    const int width = (g->tb - 1) * B + (sad ? 4 * g->groups + B + aw : 2 * S + 1 + 3 + B + 4);
-    int pt = (width + 15) & ~15;
-    if (((pt >> 4) & 1) == 0) pt += 16;
-    g->pitch = pt;
-  }
-  g->rows_alloc = g->cpp * bK + B - 1;
-  g->tile_bytes = g->rows_alloc * g->pitch;
-  g->threads = thr;
-  g->lds = 2 * (g->tile_bytes + g->tb * B * B) + 128 + 16;
-  // r = umulhi(d, magic) == d / pitch for every staged offset d (checked).
-  g->pitch_magic = (uint32_t)(0x100000000ull / (uint64_t)g->pitch) + 1u;
-  for (uint32_t d = 0; d < (uint32_t)g->tile_bytes; d += 4)
-    if ((uint32_t)(((uint64_t)d * g->pitch_magic) >> 32) != d / (uint32_t)g->pitch) return false;
-  g->wg_per_row = (g->nbx_full + g->tb - 1) / g->tb;
-  {
-    // t / wg_per_row by multiply-high for every tile index of these rows
-    const uint32_t d = (uint32_t)g->wg_per_row, m = 0xFFFFFFFFu / d + 1u;
-    const uint32_t nt = (uint32_t)g->wg_per_row * (uint32_t)(rows > 0 ? rows : 1);
-    g->magic_wpr = m;
-    for (uint32_t t = 0; t < nt; t++)
-      if ((uint32_t)(((uint64_t)t * m) >> 32) != t / d) {
-        g->magic_wpr = 0;
-        break;
-      }
-    g->magic_tb = 0xFFFFFFFFu / (uint32_t)g->tb + 1u;
-  }
-  g->aligned = (p.stride % 4 == 0) && ((uintptr_t)p.ref % 4 == 0) && ((uintptr_t)p.cur % 4 == 0);
-  // X0 = tb*B*t - S - a is 16-aligned for every tile when a = 0 (S % 4 == 0),
-  // S % 16 == 0 and tb * B % 16 == 0; rows of the ref plane 16-aligned; W % 16
-  // == 0 keeps the last in-frame granule of the last row inside the range.
-  g->tile16 = g->aligned && S % 16 == 0 && (g->tb * B) % 16 == 0 && p.width % 16 == 0 &&
-              p.stride % 16 == 0 && (uintptr_t)p.ref % 16 == 0;
-  // umulhi(t, magic_groups) == t / groups for every task index of an item.
-  g->magic_groups = 0xFFFFFFFFu / (uint32_t)g->groups + 1u;
-  const uint32_t tmax = (uint32_t)(g->tb * g->groups * g->cpp);
-  for (uint32_t t = 0; t < tmax; t++)
-    if ((uint32_t)(((uint64_t)t * g->magic_groups) >> 32) != t / (uint32_t)g->groups) return false;
-  for (uint32_t nb = 1; nb <= (uint32_t)g->tb; nb++) {  // per-item / nb, bg < tb * cpp
-    const uint32_t m = 0xFFFFFFFFu / nb + 1u;
-    for (uint32_t x = 0; x < (uint32_t)(g->tb * g->cpp); x++)
-      if (nb > 1 && (uint32_t)(((uint64_t)x * m) >> 32) != x / nb) return false;
-  }
-  g->prio = tu.prio != 0;
-  g->fair = 0;
-  g->flow_slots = 0;
-  // Wide frames: vertical strips of 16 tiles (8K 8x8: 1,024 pixels plus the
-  // window's 2S), so an XCD's contiguous run of the order is a few whole
-  // strips and its L2 holds a strip's window rows while they are reread
-  // (the row-major order fetched 2.4x the algorithmic bytes at 8K SAD).
-  g->strip_w = g->wg_per_row >= 32 && rows >= 32 ? 16 : 0;
-  if (tu.strip >= 0) g->strip_w = tu.strip;
-  // Dynamic pulls claim a workgroup's next tile when its current one starts if
-  // a tile has >= 2 passes (the id is read at the last pass, a barrier later),
-  // else two tiles ahead.  Claimed-but-unstarted tiles widen the band of rows
-  // an XCD's workgroups touch at once: ahead = 2 at 4K +-64 (128 workgroups
-  // per XCD, 3 passes) fetched 1.35x the compulsory bytes, ahead = 1
-  // 1.11x, at the same time (profiles/r04l_variants_4k.txt).
-  g->pull_ahead = (g->chunks + g->cpp - 1) / g->cpp >= 2 ? 1 : 2;
-  if (tu.ahead > 0 && (tu.ahead == 2 || g->pull_ahead == 1)) g->pull_ahead = tu.ahead;
-  *k_out = bK;
-  return true;
-}
-
-// The flow kernel (SAD, 16x16, S = 32, one 1,024-thread workgroup per CU): tiles of tb
-// blocks with all their dy chunks, tb * G * chunks a multiple of 64 (every
-// wave-task full), a ring of >= 4 slots in LDS, the ref tile in 16-byte
-// granules, and >= 2 tiles per CU (fewer leave most of the 16 waves idle: the
-// persistent item kernel takes small stripes).
-static constexpr int FLOW_LDS = 160 * 1024 - 1024;
-
-static int cu_count();
-
-bool plan_flow(const SearchArgs& p, QsadGeom* g) {
-  const int B = p.blk, S = p.range;
-  if (p.cost_kind != COST_SAD || B != 16) return false;
-  // fold (S % 8) and 16-byte tile granules (S % 16).  S <= 32: at 4K +-64 the
-  // item kernel's items are already whole waves (8 blocks x 4 chunks x 32
-  // groups) and it measured faster (1.086 vs 1.12 ms, profiles/r02p_flow_sweep.txt).
-  // The fold spreads the dx = +S column over lanes gi < K: G = S/2 >= K.
-  if (S < 16 || S % 16 || S > 32) return false;
-  if (tuning().flow == 0) return false;
-  const int nbx_full = p.width / B;
-  if (nbx_full < 1 || p.width % 16 || p.stride % 16 || (uintptr_t)p.ref % 16 || (uintptr_t)p.cur % 16)
-    return false;
-  const int D = 2 * S + 1, G = S / 2;
-  const int rows = p.block_row_end - p.block_row_begin;  // launch_jobs: every job's rows
-  const int cus = cu_count();
-  auto pitch_of = [&](int tb) {
-    int pt = ((tb - 1) * B + 4 * G + B + 4 + 15) & ~15;
-    if (((pt >> 4) & 1) == 0) pt += 16;
-    return pt;
-  };
-  auto slots_of = [&](int tb, int K) {
-    const int chunks = (D + K - 1) / K;
-    const int slot = (chunks * K + B - 1) * pitch_of(tb) + tb * B * B;
-    return min(16, (FLOW_LDS - 16 * tb * 8 - (int)sizeof(int) * 40) / slot);
-  };
-  // K = 13, whole tiles per CU, XCD-banded: the widest tile that still gives
-  // >= 6 tiles per CU (fine enough for the CUs to finish together), else the
-  // narrowest with >= 2 per CU (fewer leave most of the 16 waves idle: the
-  // persistent item kernel takes small stripes).
-  const int K = 13;
-  int best_tb = 0, best_ns = 0;
-  if (G >= 13) {
-    const int chunks = (D + 12) / 13;
-    int fine_tb = 0, fine_ns = 0;
-    for (int tb = 1; tb <= 8; tb++) {
-      if ((tb * G * chunks) % 64) continue;
-      if (tuning().plan_tb && tb != tuning().plan_tb) continue;  // tuning build
-      const int ns = slots_of(tb, 13);
-      const long tiles = (long)((nbx_full + tb - 1) / tb) * rows;
-      if (ns < 4 || tiles < 2L * cus) continue;
-      if (!best_tb) {
-        best_tb = tb;
-        best_ns = ns;
-      }
-      if (tiles >= 6L * cus) {
-        fine_tb = tb;
-        fine_ns = ns;
-      }
-    }
-    if (fine_tb) {
-      best_tb = fine_tb;
-      best_ns = fine_ns;
-    }
-    // tb = 4 (the 144-byte pitch compiled into the kernel: row addresses in
-    // the ds_read2 offsets) whenever it gives >= 6 tiles per CU: a batch of
-    // 8 1080p frames took tb = 8 at the runtime pitch, 84 us per frame
-    // against 69-78 for single frames (profiles/r03j_*)
-    const long tiles4 = (long)((nbx_full + 3) / 4) * rows;
-    if (best_tb != 4 && (4 * G * chunks) % 64 == 0 && pitch_of(4) == 144 && slots_of(4, 13) >= 4 &&
-        tiles4 >= 6L * cus && !tuning().plan_tb) {
-      best_tb = 4;
-      best_ns = slots_of(4, 13);
-    }
-  }
-  if (!best_tb) return false;
-  const int chunks = (D + K - 1) / K;
-  QsadGeom& q = *g;
-  q.tb = best_tb;
-  q.groups = G;
-  q.chunks = chunks;
-  q.cpp = chunks;
-  q.fold = 1;
-  q.nbx_full = nbx_full;
-  q.pitch = pitch_of(q.tb);
-  q.rows_alloc = chunks * K + B - 1;
-  q.tile_bytes = q.rows_alloc * q.pitch;
-  q.wg_per_row = (nbx_full + q.tb - 1) / q.tb;
-  q.magic_wpr = 0;  // the flow kernel maps a tile once per item: plain division
-  q.magic_tb = 0xFFFFFFFFu / (uint32_t)q.tb + 1u;
-  q.aligned = 1;
-  q.tile16 = 1;
-  q.threads = 1024;
-  q.dyn_tiles = 0;
-  q.pull_ahead = 2;
-  q.pitch_magic = (uint32_t)(0x100000000ull / (uint64_t)q.pitch) + 1u;
-  for (uint32_t d = 0; d < (uint32_t)q.tile_bytes; d += 16)
-    if ((uint32_t)(((uint64_t)d * q.pitch_magic) >> 32) != d / (uint32_t)q.pitch) return false;
-  q.magic_groups = 0xFFFFFFFFu / (uint32_t)G + 1u;
-  for (uint32_t t = 0; t < (uint32_t)(q.tb * G * chunks); t++)
-    if ((uint32_t)(((uint64_t)t * q.magic_groups) >> 32) != t / (uint32_t)G) return false;
-  for (uint32_t nb = 2; nb <= (uint32_t)q.tb; nb++) {
-    const uint32_t mg = 0xFFFFFFFFu / nb + 1u;
-    for (uint32_t xx = 0; xx < (uint32_t)(q.tb * chunks); xx++)
-      if ((uint32_t)(((uint64_t)xx * mg) >> 32) != xx / nb) return false;
-  }
-  const int slot = q.tile_bytes + q.tb * B * B;
-  if (tuning().flow_slots && tuning().flow_slots < best_ns) best_ns = tuning().flow_slots;
-  q.flow_slots = best_ns;
-  q.prio = tuning().prio != 0;
-  q.fair = tuning().fair != 0
-               ? (tuning().fair_lo | tuning().fair_hi << 8 | (tuning().fair > 1 ? tuning().fair : 1) << 16)
-               : 0;
-  q.strip_w = 0;
-  q.lds = best_ns * slot + best_ns * q.tb * 8 + (int)sizeof(int) * 40;
-  return q.lds <= 160 * 1024;
-}
-
 // Per-kernel launch facts, computed once per (kernel, device[, shape]) and
 // shared by every host thread (a mutex-protected list: the per-device threads
 // of multi_search and me_search_pairs plan and launch concurrently).  Setting
@@ -1688,7 +1338,7 @@ static int resident_wgs(const void* fn, int threads, int lds) {
 // CUs of the device (every device of a context is the same part): a C++11
 // function-local static, initialised once and thread-safely (multi_search and
 // me_search_pairs call the planners from one host thread per device).
-static int cu_count() {
+int cu_count() {
   static const int cus = []() {
     int dev = 0, n = 0;
     (void)hipGetDevice(&dev);
@@ -1701,12 +1351,10 @@ static int cu_count() {
 
 // One item-kernel launch over the job table jb (full-height rows and h = B/2
 // bottom rows; every job the geometry g was planned for).
-static hipError_t launch_fast(const SearchArgs& p, QsadGeom g, int K, const FlowJobs& jb,
+static hipError_t launch_fast(const SearchArgs& p, const QsadGeom& g, int K, const FlowJobs& jb,
                               hipStream_t stream) {
   const int ntiles = jb.tile_pre[jb.n];
   if (ntiles <= 0) return hipSuccess;
-  g.row0 = 0;
-  g.nrows = 0;  // per job (jb.r0, jb.tile_pre)
   dim3 block((unsigned)g.threads);
 // PP > 0: the instance with that compile-time tile pitch (row addresses in the
 // ds_read2 offset fields), taken when the plan has exactly that pitch.
@@ -1740,72 +1388,39 @@ static hipError_t launch_fast(const SearchArgs& p, QsadGeom g, int K, const Flow
 // Plans depend only on the search shape: cache them (process-wide, under a
 // mutex: the per-device threads of multi_search and me_search_pairs share
 // them) so a steady stream of same-shape searches pays the planner once.
-struct PlanKey {
-  int width, height, stride, blk, range, cost, rows, aligned;  // aligned: 1 (4 B) | 2 (16 B)
-  bool operator==(const PlanKey& o) const {
-    return width == o.width && height == o.height && stride == o.stride && blk == o.blk &&
-           range == o.range && cost == o.cost && rows == o.rows && aligned == o.aligned;
+// One ring of 8 per planner (me_valu_plan.cpp).
+enum PlanKind { PLAN_ITEM = 0, PLAN_FLOW = 1 };
+
+// The plan of `kind` for `rows` block rows of p's shape on planes of
+// alignment class ac (align_class; of every job of a batch).  K may be null.
+static bool cached_plan(PlanKind kind, const SearchArgs& p, int rows, int ac, QsadGeom* g, int* K) {
+  constexpr int N = 8;
+  struct Entry { PlanShape key; bool ok; QsadGeom g; int K; };
+  static struct { Entry e[N]; int used, next; } rings[2];
+  static std::mutex mu;
+  // what each planner reads of the class: the item kernel nothing of cur's
+  // 16-byte alignment, the flow kernel only whether everything is 16-byte aligned
+  const int all16 = ALIGN_REF16 | ALIGN_CUR16;
+  const int align = kind == PLAN_ITEM ? ac & (ALIGN_4 | ALIGN_REF16) : (ac & all16) == all16 ? ALIGN_ALL : 0;
+  const PlanShape key{p.width, p.height, p.stride, p.blk, p.range, p.cost_kind, rows, align};
+  auto& ring = rings[kind];
+  std::lock_guard<std::mutex> lk(mu);
+  const Entry* hit = nullptr;
+  for (int i = 0; i < ring.used && !hit; i++)
+    if (ring.e[i].key == key) hit = &ring.e[i];
+  if (!hit) {
+    Entry& e = ring.e[ring.next];
+    e.key = key;
+    e.K = 13;
+    e.ok = kind == PLAN_ITEM ? plan_fast(key, cu_count(), tuning(), &e.g, &e.K)
+                             : plan_flow(key, cu_count(), tuning(), &e.g);
+    ring.next = (ring.next + 1) % N;
+    if (ring.used < N) ring.used++;
+    hit = &e;
   }
-};
-struct PlanEntry {
-  PlanKey key;
-  bool ok;
-  QsadGeom g;
-  int K;
-};
-
-static bool cached_plan(const SearchArgs& p, QsadGeom* g, int* K) {
-  constexpr int N = 8;
-  static PlanEntry cache[N];
-  static int used = 0, next = 0;
-  static std::mutex mu;
-  const int aligned =
-      ((p.stride % 4 == 0) && ((uintptr_t)p.ref % 4 == 0) && ((uintptr_t)p.cur % 4 == 0)) |
-      (((p.stride % 16 == 0) && ((uintptr_t)p.ref % 16 == 0)) << 1);
-  const PlanKey key{p.width, p.height, p.stride, p.blk, p.range, p.cost_kind,
-                    p.block_row_end - p.block_row_begin, aligned};
-  std::lock_guard<std::mutex> lk(mu);
-  for (int i = 0; i < used; i++)
-    if (cache[i].key == key) {
-      *g = cache[i].g;
-      *K = cache[i].K;
-      return cache[i].ok;
-    }
-  PlanEntry e;
-  e.key = key;
-  e.ok = plan_fast(p, &e.g, &e.K);
-  cache[next] = e;
-  next = (next + 1) % N;
-  if (used < N) used++;
-  *g = e.g;
-  *K = e.K;
-  return e.ok;
-}
-
-static bool cached_flow_plan(const SearchArgs& p, QsadGeom* g) {
-  constexpr int N = 8;
-  static PlanEntry cache[N];
-  static int used = 0, next = 0;
-  static std::mutex mu;
-  const int aligned = ((p.stride % 16 == 0) && ((uintptr_t)p.ref % 16 == 0) &&
-                       ((uintptr_t)p.cur % 16 == 0)) ? 3 : 0;
-  const PlanKey key{p.width, p.height, p.stride, p.blk, p.range, p.cost_kind,
-                    p.block_row_end - p.block_row_begin, aligned};
-  std::lock_guard<std::mutex> lk(mu);
-  for (int i = 0; i < used; i++)
-    if (cache[i].key == key) {
-      *g = cache[i].g;
-      return cache[i].ok;
-    }
-  PlanEntry e;
-  e.key = key;
-  e.ok = plan_flow(p, &e.g);
-  e.K = 13;
-  cache[next] = e;
-  next = (next + 1) % N;
-  if (used < N) used++;
-  *g = e.g;
-  return e.ok;
+  *g = hit->g;
+  if (K) *K = hit->K;
+  return hit->ok;
 }
 
 // The job table of jobs [0, n) (n <= MAX_JOBS; rows [r0, r1) each, already
@@ -1822,10 +1437,8 @@ static FlowJobs job_table(const SearchArgs& p, int wg_per_row, const SearchJob* 
     jb.r0[j] = J.r0;
     jb.ref_row0[j] = J.ref_row0;
     jb.cur_row0[j] = J.cur_row0;
-    // bytes the job's descriptors may read: its resident rows (include/me.h)
-    const int ref_end = J.r1 * B + S < H ? J.r1 * B + S : H, cur_end = J.r1 * B < H ? J.r1 * B : H;
-    jb.ref_bytes[j] = (uint32_t)((long)(ref_end - J.ref_row0 - 1) * p.stride + p.width);
-    jb.cur_bytes[j] = (uint32_t)((long)(cur_end - J.cur_row0 - 1) * p.stride + p.width);
+    jb.ref_bytes[j] = ref_resident_bytes(J.r1, B, S, H, J.ref_row0, p.stride, p.width);
+    jb.cur_bytes[j] = cur_resident_bytes(J.r1, B, H, J.cur_row0, p.stride, p.width);
     jb.ref[j] = J.ref;
     jb.cur[j] = J.cur;
     jb.mv[j] = J.mv;
@@ -1837,13 +1450,11 @@ static FlowJobs job_table(const SearchArgs& p, int wg_per_row, const SearchJob* 
 
 // One flow-kernel launch over jobs [0, n) (full-height rows and h = B/2
 // bottom rows only; n <= MAX_JOBS).
-static hipError_t launch_flow(const SearchArgs& p, QsadGeom g, const SearchJob* jobs, int n,
+static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const SearchJob* jobs, int n,
                               hipStream_t stream) {
   const FlowJobs jb = job_table(p, g.wg_per_row, jobs, n);
   const int ntiles = jb.tile_pre[jb.n];
   if (ntiles <= 0) return hipSuccess;
-  g.row0 = 0;
-  g.nrows = 0;  // per job (jb.r0)
   const int nwg = ntiles > cu_count() ? cu_count() : ntiles;  // one per CU, at most one per tile
   // 144: the pitch of the 4-block tiles 1080p +-32 gets (row addresses in
   // the ds_read2 offsets); any other pitch takes the runtime-pitch body
@@ -1876,11 +1487,9 @@ static SearchArgs job_args(const SearchArgs& base, const SearchJob& J) {
   q.block_row_end = J.r1;
   q.mv = J.mv;
   q.cost = J.cost;
-  const int B = base.blk, S = base.range, H = base.height;
-  const int ref_end = J.r1 * B + S < H ? J.r1 * B + S : H, cur_end = J.r1 * B < H ? J.r1 * B : H;
-  const long ref_rows = ref_end - J.ref_row0, cur_rows = cur_end - J.cur_row0;
-  q.ref_bytes = ref_rows > 0 ? (uint32_t)((ref_rows - 1) * (long)base.stride + base.width) : 0;
-  q.cur_bytes = cur_rows > 0 ? (uint32_t)((cur_rows - 1) * (long)base.stride + base.width) : 0;
+  q.ref_bytes = ref_resident_bytes(J.r1, base.blk, base.range, base.height, J.ref_row0, base.stride,
+                                   base.width);
+  q.cur_bytes = cur_resident_bytes(J.r1, base.blk, base.height, J.cur_row0, base.stride, base.width);
   return q;
 }
 
@@ -1892,24 +1501,36 @@ static int qsad_rows_end(const SearchArgs& p, int r1) {
   return r1 == nby && h_last != p.blk && h_last != p.blk / 2 ? r1 - 1 : r1;
 }
 
+// The rows and columns of job J that a qsad kernel planned with nbx_full full
+// blocks per row leaves (a bottom row of another height, the partial right
+// column): the generic kernel.
+static hipError_t launch_leftovers(const SearchArgs& base, const SearchJob& J, int nbx_full,
+                                   hipStream_t stream) {
+  const int rq1 = qsad_rows_end(base, J.r1);
+  if (rq1 == J.r1 && nbx_full >= base.nbx) return hipSuccess;  // nothing left: the usual case
+  const SearchArgs q = job_args(base, J);
+  if (rq1 < J.r1) {
+    const hipError_t e = launch_generic(q, 0, nbx_full, rq1, J.r1 - rq1, stream);
+    if (e != hipSuccess) return e;
+  }
+  if (nbx_full < base.nbx)
+    return launch_generic(q, nbx_full, base.nbx - nbx_full, J.r0, J.r1 - J.r0, stream);
+  return hipSuccess;
+}
+
 // The persistent item kernel (and the generic kernel for what it leaves).
 static hipError_t launch_items(const SearchArgs& p, hipStream_t stream, int* used_fast) {
   const int r0 = p.block_row_begin, r1 = p.block_row_end;
   QsadGeom g;
   int K = 0;
-  if (!cached_plan(p, &g, &K)) return launch_generic(p, 0, p.nbx, r0, r1 - r0, stream);
-  const int rq1 = qsad_rows_end(p, r1);
-  const SearchJob J{p.ref, p.ref_row0, p.cur, p.cur_row0, r0, rq1, p.mv, p.cost};
-  hipError_t e = launch_fast(p, g, K, job_table(p, g.wg_per_row, &J, 1), stream);
+  if (!cached_plan(PLAN_ITEM, p, r1 - r0, align_class(p.stride, p.ref, p.cur), &g, &K))
+    return launch_generic(p, 0, p.nbx, r0, r1 - r0, stream);
+  SearchJob J{p.ref, p.ref_row0, p.cur, p.cur_row0, r0, qsad_rows_end(p, r1), p.mv, p.cost};
+  const hipError_t e = launch_fast(p, g, K, job_table(p, g.wg_per_row, &J, 1), stream);
   if (e != hipSuccess) return e;
   if (used_fast) *used_fast = 1;
-  if (rq1 < r1) {
-    e = launch_generic(p, 0, g.nbx_full, rq1, r1 - rq1, stream);
-    if (e != hipSuccess) return e;
-  }
-  if (g.nbx_full < p.nbx)  // partial right column
-    return launch_generic(p, g.nbx_full, p.nbx - g.nbx_full, r0, r1 - r0, stream);
-  return hipSuccess;
+  J.r1 = r1;
+  return launch_leftovers(p, J, g.nbx_full, stream);
 }
 
 // SAD jobs on the flow kernel where its plan (over every job's rows) takes
@@ -1925,16 +1546,14 @@ static bool launch_flow_jobs(const SearchArgs& base, const SearchJob* jobs, int 
                              hipError_t* err) {
   *err = hipSuccess;
   if (base.cost_kind != COST_SAD || n < 1) return false;
-  int rows = 0;
+  int rows = 0;  // the planner counts tiles over every job's rows
   for (int i = 0; i < n; i++) {
     rows += jobs[i].r1 - jobs[i].r0;
     if ((uintptr_t)jobs[i].ref % 16 || (uintptr_t)jobs[i].cur % 16) return false;
   }
-  SearchArgs probe = job_args(base, jobs[0]);
-  probe.block_row_begin = 0;
-  probe.block_row_end = rows;  // the planner counts tiles over every job's rows
   QsadGeom g;
-  if (!cached_flow_plan(probe, &g)) return false;
+  if (!cached_plan(PLAN_FLOW, base, rows, align_class(base.stride, jobs[0].ref, jobs[0].cur), &g, nullptr))
+    return false;
   long total = 0;
   for (int i = 0; i < n; i++)
     total += (long)g.wg_per_row * (qsad_rows_end(base, jobs[i].r1) - jobs[i].r0);
@@ -1958,21 +1577,9 @@ static bool launch_flow_jobs(const SearchArgs& base, const SearchJob* jobs, int 
   }
   if (m && *err == hipSuccess) *err = launch_flow(base, g, fj, m, stream);
   // the rows and columns the flow kernel leaves, job by job
-  for (int i = 0; i < n && *err == hipSuccess; i++) {
-    const SearchArgs q = job_args(base, jobs[i]);
-    const int rq1 = qsad_rows_end(base, jobs[i].r1);
-    if (rq1 < jobs[i].r1) *err = launch_generic(q, 0, g.nbx_full, rq1, jobs[i].r1 - rq1, stream);
-    if (*err == hipSuccess && g.nbx_full < base.nbx)
-      *err = launch_generic(q, g.nbx_full, base.nbx - g.nbx_full, jobs[i].r0,
-                            jobs[i].r1 - jobs[i].r0, stream);
-  }
+  for (int i = 0; i < n && *err == hipSuccess; i++)
+    *err = launch_leftovers(base, jobs[i], g.nbx_full, stream);
   return true;
-}
-
-// Alignment class of a job's planes (the item planner's key, cached_plan).
-static int align_class(const SearchArgs& p, const uint8_t* ref, const uint8_t* cur) {
-  return ((p.stride % 4 == 0) && ((uintptr_t)ref % 4 == 0) && ((uintptr_t)cur % 4 == 0)) |
-         (((p.stride % 16 == 0) && ((uintptr_t)ref % 16 == 0)) << 1);
 }
 
 // VALU jobs the item kernel takes (SAD, or SSD off the matrix cores) in one
@@ -1984,18 +1591,17 @@ static bool launch_item_jobs(const SearchArgs& base, const SearchJob* jobs, int 
                              hipStream_t stream, hipError_t* err) {
   *err = hipSuccess;
   if (n < 2 || (base.cost_kind != COST_SAD && base.cost_kind != COST_SSD)) return false;
-  const int ac = align_class(base, jobs[0].ref, jobs[0].cur);
-  int rows = 0;
+  // (the item planner reads nothing of cur's 16-byte alignment)
+  const int item_bits = ALIGN_4 | ALIGN_REF16;
+  const int ac = align_class(base.stride, jobs[0].ref, jobs[0].cur) & item_bits;
+  int rows = 0;  // the planner counts tiles over every job's rows
   for (int i = 0; i < n; i++) {
     rows += jobs[i].r1 - jobs[i].r0;
-    if (align_class(base, jobs[i].ref, jobs[i].cur) != ac) return false;
+    if ((align_class(base.stride, jobs[i].ref, jobs[i].cur) & item_bits) != ac) return false;
   }
-  SearchArgs probe = job_args(base, jobs[0]);
-  probe.block_row_begin = 0;
-  probe.block_row_end = rows;  // the planner counts tiles over every job's rows
   QsadGeom g;
   int K = 0;
-  if (!cached_plan(probe, &g, &K)) return false;
+  if (!cached_plan(PLAN_ITEM, base, rows, ac, &g, &K)) return false;
   // Every job shares the launch, however large: with whole frames per XCD band
   // the bands need no halo rows.  8K 8x8 +-128, 16 frames: 17.09 ms and 70.7 MB
   // read per frame in one row-major launch, against 17.26 ms and 89.9 MB one
@@ -2015,14 +1621,8 @@ static bool launch_item_jobs(const SearchArgs& base, const SearchJob* jobs, int 
     *err = launch_fast(base, g, K, job_table(base, g.wg_per_row, fj, m), stream);
   }
   // the rows and columns the item kernel leaves, job by job
-  for (int i = 0; i < n && *err == hipSuccess; i++) {
-    const SearchArgs q = job_args(base, jobs[i]);
-    const int rq1 = qsad_rows_end(base, jobs[i].r1);
-    if (rq1 < jobs[i].r1) *err = launch_generic(q, 0, g.nbx_full, rq1, jobs[i].r1 - rq1, stream);
-    if (*err == hipSuccess && g.nbx_full < base.nbx)
-      *err = launch_generic(q, g.nbx_full, base.nbx - g.nbx_full, jobs[i].r0,
-                            jobs[i].r1 - jobs[i].r0, stream);
-  }
+  for (int i = 0; i < n && *err == hipSuccess; i++)
+    *err = launch_leftovers(base, jobs[i], g.nbx_full, stream);
   return true;
 }
 

@@ -7,6 +7,8 @@
 // and rejects malformed values with a message on stderr (the automatic setting
 // stays).  tools/plan_sweep.py, tools/dyn_sweep.sh and tools/dbg/* select it
 // with ME_HIP_LIB=libme_hip_tune.so.
+// The VALU launch planners (me_valu_plan.cpp) take a `const Tuning&` argument
+// and never call tuning(): their callers pass it, the CPU tests a default one.
 #pragma once
 
 #include <atomic>

@@ -9,7 +9,10 @@
 //   - the file readers (me_io.cpp) fed truncated, corrupt and hostile files:
 //     every one must come back as ME_EIO / ME_EINVAL, never a crash or an
 //     out-of-bounds access (the reference's reader never checks its fopen,
-//     src/common/utils.c:61-67).
+//     src/common/utils.c:61-67);
+//   - the VALU launch planners (me_valu_plan.cpp: plan_fast, plan_flow) over
+//     seeded random shapes, alignment classes, CU counts and tuning overrides,
+//     checking what the kernels rely on in every accepted plan.
 // Exit status 0 and "san ok" on success; the sanitizers abort otherwise.
 #include <stdint.h>
 #include <stdio.h>
@@ -21,7 +24,9 @@
 #include <vector>
 
 #include "me.h"
+#include "me_geom.h"
 #include "me_oracle.h"
+#include "me_tuning.h"
 
 #define CHECK(x)                                                   \
   do {                                                             \
@@ -158,10 +163,112 @@ static void files() {
   unlink(yuv.c_str());
 }
 
+// umulhi(x, m) == x / d for x = 0, step, ... < n
+static bool divides(uint32_t m, uint32_t d, uint32_t n, uint32_t step) {
+  for (uint32_t x = 0; x < n; x += step)
+    if ((uint32_t)(((uint64_t)x * m) >> 32) != x / d) return false;
+  return true;
+}
+
+// What the item and flow kernels rely on in an accepted plan.
+// (min_slots: 4, or less where a tuning override cuts the flow kernel's ring)
+static void check_plan(const me::PlanShape& s, const me::QsadGeom& g, int K, bool flow,
+                       int min_slots = 4) {
+  CHECK(g.row0 == 0 && g.nrows == 0);
+  CHECK(g.tb >= 1 && g.groups >= 1 && g.cpp >= 1 && g.chunks >= g.cpp);
+  CHECK(g.pitch % 32 == 16);
+  CHECK(g.rows_alloc == g.cpp * K + s.blk - 1);
+  CHECK(g.tile_bytes == g.rows_alloc * g.pitch);
+  CHECK(g.nbx_full == s.width / s.blk);
+  CHECK(g.wg_per_row == (g.nbx_full + g.tb - 1) / g.tb);
+  // the magic divisors, each over the range its comment in QsadGeom states
+  CHECK(divides(g.pitch_magic, (uint32_t)g.pitch, (uint32_t)g.tile_bytes, flow ? 16 : 4));
+  CHECK(divides(g.magic_groups, (uint32_t)g.groups, (uint32_t)(g.tb * g.groups * g.cpp), 1));
+  if (g.tb > 1)  // (one-block items take no division)
+    CHECK(divides(g.magic_tb, (uint32_t)g.tb, (uint32_t)(g.tb * g.cpp), 1));
+  if (g.magic_wpr)
+    CHECK(divides(g.magic_wpr, (uint32_t)g.wg_per_row, (uint32_t)(g.wg_per_row * s.rows), 1));
+  if (flow) {
+    CHECK(g.lds <= 160 * 1024);
+    CHECK(g.flow_slots >= min_slots && g.flow_slots <= 16);
+    CHECK((g.tb * g.groups * g.chunks) % 64 == 0);
+    CHECK(g.threads == 1024 && g.fold == 1 && g.tile16 == 1 && g.magic_wpr == 0);
+  } else {
+    CHECK(g.lds <= me::QSAD_LDS_BUDGET + 16);
+    CHECK(g.flow_slots == 0);
+    CHECK(!g.tile16 || g.aligned);
+  }
+}
+
+static void valu_planners() {
+  const int cu_counts[] = {64, 256, 304};
+  const int odd_blks[] = {0, 4, 12, 32};
+  int accepted = 0;
+  for (int t = 0; t < 2500; t++) {
+    me::PlanShape s;
+    s.width = 1 + (int)(next_u64() % 8000);
+    s.height = 1 + (int)(next_u64() % 4400);
+    s.stride = s.width + (next_u64() % 3 ? 0 : (int)(next_u64() % 64));
+    s.blk = next_u64() % 8 ? (next_u64() % 2 ? 16 : 8) : odd_blks[next_u64() % 4];
+    s.range = (int)(next_u64() % 301);
+    if (next_u64() % 2) s.range &= ~15;  // the fold and flow rules want multiples of 4, 8, 16
+    if (next_u64() % 4 == 0) s.width &= ~15, s.stride = s.width;
+    s.cost = (int)(next_u64() % 2);
+    s.rows = 1 + (int)(next_u64() % 9000);
+    // planes at every alignment (never dereferenced)
+    const uintptr_t mods[] = {0, 0, 0, 4, 8, 1, 2};
+    s.align = me::align_class(s.stride, (const void*)(0x10000 + mods[next_u64() % 7]),
+                              (const void*)(0x20000 + mods[next_u64() % 7]));
+    const int cus = cu_counts[next_u64() % 3];
+    // every fourth shape under a tuning override: refused, or as forced
+    me::Tuning tu;
+    if (t % 4 == 3) {
+      const int ks[] = {0, 5, 8, 11, 13, 26};
+      tu.plan_k = ks[next_u64() % 6];
+      tu.plan_tb = (int)(next_u64() % 17);
+      tu.plan_fold = (int)(next_u64() % 3) - 1;
+    }
+    me::QsadGeom g;
+    int K = 0;
+    if (me::plan_fast(s, cus, tu, &g, &K)) {
+      accepted++;
+      CHECK(s.blk == 8 || s.blk == 16);
+      CHECK(s.range >= 1 && s.range <= 255 && s.width >= s.blk);
+      check_plan(s, g, K, false);
+      CHECK(!tu.plan_k || K == tu.plan_k);
+      CHECK(!tu.plan_tb || g.tb == tu.plan_tb);
+      CHECK(tu.plan_fold < 0 || g.fold == tu.plan_fold);
+    }
+    if (me::plan_flow(s, cus, tu, &g)) {
+      accepted++;
+      CHECK(s.cost == me::COST_SAD && s.blk == 16 && s.range == 32 && s.align == me::ALIGN_ALL);
+      CHECK((long)g.wg_per_row * s.rows >= 2L * cus);
+      check_plan(s, g, 13, true);
+      CHECK(!tu.plan_tb || g.tb == tu.plan_tb);
+    }
+  }
+  CHECK(accepted > 1000);
+  // the flow kernel's shapes are rare in the draw above: its own pass
+  for (int t = 0; t < 400; t++) {
+    me::PlanShape s{16 * (1 + (int)(next_u64() % 500)), 1080, 0, 16, 32, me::COST_SAD,
+                    1 + (int)(next_u64() % 2000), me::ALIGN_ALL};
+    s.stride = s.width + 16 * (int)(next_u64() % 4);
+    me::Tuning tu;
+    if (t % 4 == 3) tu.plan_tb = 1 + (int)(next_u64() % 8), tu.flow_slots = 2 + (int)(next_u64() % 15);
+    me::QsadGeom g;
+    if (!me::plan_flow(s, cu_counts[t % 3], tu, &g)) continue;
+    // the override may cut the ring below the 4 slots the planner asks for
+    if (tu.flow_slots) CHECK(g.flow_slots <= tu.flow_slots);
+    check_plan(s, g, 13, true, tu.flow_slots && tu.flow_slots < 4 ? tu.flow_slots : 4);
+    CHECK(!tu.plan_tb || g.tb == tu.plan_tb);
+  }
+}
+
 int main() {
   pool();
   planner();
   files();
+  valu_planners();
   printf("san ok\n");
   return 0;
 }

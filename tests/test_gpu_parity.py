@@ -604,3 +604,44 @@ def test_random_job_tables_equal_per_job_searches(engine):
             np.testing.assert_array_equal(mv.cpu().numpy(), mv1.cpu().numpy(), err_msg=msg)
             np.testing.assert_array_equal(co.cpu().numpy(), co1.cpu().numpy(), err_msg=msg)
     engine.device_check()
+
+
+@pytest.mark.parametrize("cost", ["sad", "ssd"])
+def test_stripe_jobs_of_different_alignment_run_job_by_job(engine, cost):
+    """Two jobs of one me_search_stripes_device call whose planes differ in
+    alignment class (job 0's 16-byte aligned, job 1's ref one byte into a
+    larger buffer) cannot share an item-kernel plan: the call falls back to
+    one search per job (launch_item_jobs -> launch_search), and each job
+    equals the oracle.  SSD on the VALU kernels, the path that plans items."""
+    import torch
+    w, h, stride, blk, span = 96, 64, 112, 16, 8
+    nb = me.num_blocks(w, h, blk)
+    rng = np.random.default_rng(7)
+
+    def plane(img, offset):
+        buf = torch.from_numpy(rng.integers(0, 256, h * stride + 16, dtype=np.uint8)).cuda()
+        t = buf[offset:offset + h * stride].view(h, stride)
+        t[:, :w] = torch.from_numpy(img).cuda()
+        return t
+
+    jobs, want = [], []
+    for j, ref_offset in enumerate((0, 1)):
+        ref, cur = synth.frame_pair(w, h, 90 + j, 3 - 5 * j, -2 + 3 * j)
+        rt, ct = plane(ref, ref_offset), plane(cur, 0)
+        assert rt.data_ptr() % 16 == ref_offset and ct.data_ptr() % 16 == 0
+        mv = torch.full((nb, 2), -5, dtype=torch.int16, device="cuda")
+        co = torch.zeros(nb, dtype=torch.int32, device="cuda")
+        jobs.append((rt, 0, ct, 0, 0, h // blk, mv, co))
+        want.append(O.full_search(ref, cur, blk, span, cost))
+    if cost == "ssd":
+        me.set_kernel_path("valu")
+    try:
+        engine.search_stripes_device(w, h, blk, span, cost, jobs, stride=stride)
+        torch.cuda.synchronize()
+        assert me.last_search_path() == "valu"
+    finally:
+        me.set_kernel_path("auto")
+    for j, (job, (omv, oco, _)) in enumerate(zip(jobs, want)):
+        np.testing.assert_array_equal(job[6].cpu().numpy(), omv, err_msg=f"{cost} job {j}")
+        np.testing.assert_array_equal(job[7].cpu().numpy().view(np.uint32), oco, err_msg=f"{cost} job {j}")
+    engine.device_check()

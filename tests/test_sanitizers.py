@@ -3,8 +3,9 @@
 `make -C oracle asan tsan` builds oracle/san_main.cc against the oracle's
 pthread pool and libme_hip's host-only C++ (me_plan.cpp: stripe planner and
 candidate counts; me_io.cpp: the YUV and MEMV readers fed truncated, corrupt
-and hostile files) under AddressSanitizer + UBSan and under ThreadSanitizer;
-both runs must finish clean."""
+and hostile files; me_valu_plan.cpp: the VALU launch planners over random
+shapes, with the invariants of every accepted plan) under AddressSanitizer +
+UBSan and under ThreadSanitizer; both runs must finish clean."""
 import os
 import subprocess
 
