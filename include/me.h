@@ -30,6 +30,9 @@
  *     searched with the reference's float accumulation replayed exactly.
  *   - ME_COST_SAD: same loops and tie rule with |cur - ref| (the reference
  *     has no SAD; parity is against the repo's CPU restatement).
+ *     The 1080p-class kernel skips candidates an exact lower bound proves
+ *     strictly worse than one already evaluated; vectors and costs remain
+ *     the exhaustive search's, bit for bit.
  *   - ME_COST_SSIM: the reference's SSIM search (src/common/ssim.c:3-108,
  *     src/cpu/main_ssim.c:15-29), float arithmetic replayed in its order.
  *

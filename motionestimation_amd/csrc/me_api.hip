@@ -77,6 +77,9 @@ static Tuning read_tuning() {
   env_int("ME_ITEM_BATCH", 0, 1, &t.item_batch);
   env_int("ME_FAIR", 0, 3, &t.fair);
   env_int("ME_FLOW_ONE", 0, 1, &t.flow_one);
+  env_int("ME_PRUNE", 0, 2, &t.prune);
+  env_int("ME_PRUNE_BYPASS", 0, 1, &t.prune_bypass);
+  t.prune_stats = 1;
   env_int("ME_MFMA_BATCH", 0, 1, &t.mfma_batch);
   env_int("ME_MFMA_S2K", 0, 1, &t.mfma_s2k);
   env_int("ME_MFMA_S2R", 1, 2, &t.mfma_s2r);
@@ -804,6 +807,26 @@ me_status me_device_check(me_ctx* c) {
   (void)hipSetDevice(prev);
   return s;
 }
+
+#ifdef ME_TUNING
+// Tuning build only (tools/sad_prune_ab.py): the pruning flow kernel's counts
+// on the context's first device since the last call -- live lane-tasks, all
+// lane-tasks, bypassed items, items -- read after the device is idle, then
+// zeroed.
+extern "C" int me_debug_prune_stats(me_ctx* c, uint32_t* out4) {
+  if (!c || c->devs.empty() || !out4) return ME_EINVAL;
+  Dev& d = c->devs[0];
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  int rc = ME_OK;
+  if (hipSetDevice(d.id) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(out4, d.sched + me::SCHED_PRUNE, 16, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemset(d.sched + me::SCHED_PRUNE, 0, 16) != hipSuccess)
+    rc = ME_EDEVICE;
+  (void)hipSetDevice(prev);
+  return rc;
+}
+#endif
 
 // A captured step: the graph plus what its searches point into.
 struct me_graph {

@@ -93,7 +93,24 @@ struct QsadGeom {
                    // wave-task others have overtaken by >= lo / hi pulls raises its
                    // issue priority to 1 / 2 (checked every 4 rows; 8 / 16 by
                    // default) in launches with slot refills (mode 1)
+  // me_flow_kernel, candidate pruning by the exact sub-block bound (0: every
+  // lane-task runs, the ring is flow_slots slots in lds bytes):
+  int prune;         // 1: on; 2: verify (every lane-task runs, a wrongly dead one is reported)
+  int prune_bypass;  // 1: after a run of items the bound could not thin, skip it and re-probe
+  int prune_stats;   // 1: live / total lane-tasks and bypassed items counted in sched[SCHED_PRUNE..]
+  int prune_slots;   // ring slots when pruning (each slot carries FLOW_PRUNE_BYTES of bound scratch)
+  int prune_lds;     // dynamic LDS bytes of the pruning launch
 };
+
+// Bound scratch of one ring slot of the pruning flow kernel: four x-phase
+// planes of 77 rows x 32 box-sum bytes (the live list overlays them once the
+// bound is done), minlb[5][4][16] u32 and the cur blocks' 4 x 16 box-sum bytes.
+constexpr int FLOW_PRUNE_QROWS = 77;
+constexpr int FLOW_PRUNE_PLANE = FLOW_PRUNE_QROWS * 32;
+constexpr int FLOW_PRUNE_MINLB = 4 * FLOW_PRUNE_PLANE;
+constexpr int FLOW_PRUNE_QCUR = FLOW_PRUNE_MINLB + 320 * 4;
+constexpr int FLOW_PRUNE_BYTES = FLOW_PRUNE_QCUR + 64;
+constexpr int FLOW_CTL_BYTES = 256;  // the pruning launch's control block (FlowCtl)
 
 // A search job: block rows [r0, r1) of one frame (or row stripe), its planes
 // (ref / cur hold frame rows from ref_row0 / cur_row0, as in SearchArgs) and

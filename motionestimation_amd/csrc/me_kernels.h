@@ -16,6 +16,10 @@ namespace me {
 constexpr int SCHED_WORDS = 32;
 constexpr int SCHED_ARRIVE = 16;
 constexpr int SCHED_ERR = 31;
+// Tuning build only (QsadGeom::prune_stats): the pruning flow kernel's counts
+// since the words were last zeroed: live lane-tasks, all lane-tasks, items
+// whose bound was bypassed, items.
+constexpr int SCHED_PRUNE = 24;
 
 // Write block `out`'s MV from a merged 64-bit key (cost << 32 | (dy + 32768)
 // << 16 | (dx + 32768)): one 4-byte store of the (mvx, mvy) int16 pair when the

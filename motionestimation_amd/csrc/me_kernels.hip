@@ -953,7 +953,16 @@ struct FlowCtl {
   uint32_t next;       // wave-tasks handed out
   uint32_t ready[16];  // item index + 1 published in the slot
   uint32_t done[16];   // wave-tasks of the slot's item finished
+  // The pruning switches (PF_*), copied here once: read from LDS where they
+  // are used, they occupy no SGPRs across the task loop (kernel arguments would).
+  uint32_t pflags;
+  uint32_t run;        // items in a row the bound could not thin (bypass)
+  // pruning launches only (the plain launch's LDS ends above)
+  uint32_t live[16];   // live lane-tasks of the slot's item (its list's length)
+  uint32_t stats[4];   // tuning build: live, all lane-tasks, bypassed items, items (flushed at the end)
 };
+enum { PF_ON = 1, PF_VERIFY = 2, PF_BYPASS = 4, PF_STATS = 8 };
+static_assert(sizeof(FlowCtl) <= FLOW_CTL_BYTES, "control block of the pruning launch");
 
 // Tile of the flow kernel's launch -> its item (all dy chunks: one pass).
 template <int B, int K>
@@ -1008,13 +1017,302 @@ __device__ __forceinline__ int flow_tasks(const SearchArgs& p, const QsadGeom& g
   return ((lc1 - lc0) * it.nb * g.groups + 63) >> 6;
 }
 
+// ------------------------------------------------------ flow: the bound phase
+// Pruning by an exact lower bound.  Let q(.) be the 4x4 box sum >> 4; a 16x16
+// block has 16 sub-blocks sb.  By the triangle inequality per sub-block, and
+// with at most 15 lost to each of the 16 shifts,
+//     SAD(c, r) >= sum_sb |sum c_sb - sum r_sb| >= 16 * sum_sb |q(c_sb) - q(r_sb)| - 240 = LB.
+// The wave that staged an item runs this before it publishes the slot:
+//   1. q of the whole staged window as four byte planes by x phase (plane k
+//      holds columns = k mod 4), and q of the cur blocks' 16 sub-blocks;
+//   2. sum_sb |..| of every VALID candidate, 4 candidates per qsad (4 qsads per
+//      candidate row: one per sub-block row), min-reduced into minlb[lc][b][gi]
+//      per lane-task, the fold column (dx = +S) into the lane-task that owns it;
+//   3. the exact SAD of two seeds per block, (0, 0) and the candidate of the
+//      smallest bound, merged into the slot's keys like any lane-task's result;
+//      U_b = the seeded key's cost;
+//   4. the list of the lane-tasks with 16 * minlb - 240 <= U_b (signed), in
+//      index order (so a full list is the identity).
+// Exactness: a lane-task is left out only if every valid candidate in it has
+// LB > U_b; U_b is the exact SAD of a valid candidate of block b already in
+// keys; LB <= SAD, so every skipped candidate has SAD > U_b and can neither
+// win nor tie.  Equality is never pruned.  Invalid (clamped-out) candidates
+// enter no minimum: they never seed and never keep a lane-task alive.
+// Items of the h = B/2 bottom row are not bounded: all their lane-tasks live.
+// Entry of minlb: q-sum << 7 | dy index in the chunk << 3 | x phase (4: fold).
+typedef unsigned short flow_us2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_key(uint32_t a, uint32_t j) {  // per u16: a * 16 + j
+  const flow_us2 v = __builtin_bit_cast(flow_us2, a) * (flow_us2)(16) + (flow_us2)((unsigned short)j);
+  return __builtin_bit_cast(uint32_t, v);
+}
+__device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) {
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(flow_us2, a),
+                                                                __builtin_bit_cast(flow_us2, b)));
+}
+// Lane l's value of lane l ^ X (X < 32) by ds_swizzle: needs no lane id, which
+// the compiler would keep in a VGPR across the 128-VGPR task loop.
+template <int X>
+__device__ __forceinline__ uint32_t swz_xor(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (X << 10) | 0x1F);
+}
+__device__ __forceinline__ void lds_fence() {  // this wave's LDS writes before its later reads
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <int B, int K>
+__device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& g, const Item& it,
+                                           uint8_t* buf, uint64_t* keys, FlowCtl* ctl, int slot) {
+  constexpr int S = 32, G = 16, TB = 4, P = 144;
+  static_assert(B == 16 && K == 13, "bound scratch layout");
+  const int lane = fresh_tid() & 63;
+  uint8_t* pr = buf + g.tile_bytes + TB * B * B;
+  uint16_t* list = reinterpret_cast<uint16_t*>(pr);  // overlays the planes (dead by then)
+  uint32_t* minlb = reinterpret_cast<uint32_t*>(pr + FLOW_PRUNE_MINLB);
+  uint32_t* qcur = reinterpret_cast<uint32_t*>(pr + FLOW_PRUNE_QCUR);
+  const uint32_t* cur = reinterpret_cast<const uint32_t*>(buf + g.tile_bytes);
+  const int dymin = max(-S, -it.tly), dymax = min(S, p.height - it.h - it.tly);
+  const int lc0 = max(0, (dymin + S) / K), lc1 = min(it.nch, (dymax + S) / K + 1);
+  const int valid_lanes = (lc1 - lc0) * it.nb * G;
+  const int nw = (valid_lanes + 63) >> 6;
+  const int pf = __builtin_amdgcn_readfirstlane((int)ctl->pflags);
+  const bool verify = (pf & PF_VERIFY) != 0, stats = (pf & PF_STATS) != 0;
+  uint8_t* dead = pr + 640;                                   // verify: [320] flags
+  uint32_t* ub = reinterpret_cast<uint32_t*>(pr + 960);       // verify: U_b
+
+  // Bypass: after 4 items in a row that stayed more than 3/4 live the bound is
+  // skipped for 96 items, then ONE item probes again (run 3 -> 4 by
+  // compare-and-swap: the bound phases of the other slots keep bypassing).
+  int run = 0;
+  bool prober = false;
+  if (pf & PF_BYPASS) {
+    run = __builtin_amdgcn_readfirstlane(
+        (int)__hip_atomic_load(&ctl->run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    if (run == 3 && it.h == B) {
+      uint32_t old = 3u;
+      if (lane == 0)
+        __hip_atomic_compare_exchange_strong(&ctl->run, &old, 4u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+      run = __builtin_amdgcn_readfirstlane((int)old);
+      prober = run == 3;
+    }
+  }
+  const bool bypass = it.h == B && run >= 4;
+  if (it.h != B || bypass) {
+    for (int r = 0; r < nw; r++) {
+      const int idx = 64 * r + lane;
+      if (idx < valid_lanes) list[idx] = (uint16_t)idx;
+      if (verify && idx < valid_lanes) dead[idx] = 0;
+    }
+    if (lane == 0) {
+      ctl->live[slot] = (uint32_t)valid_lanes;
+      if (bypass &&
+          __hip_atomic_fetch_add(&ctl->run, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + 1u >= 100u)
+        __hip_atomic_store(&ctl->run, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (stats) {
+        atomicAdd(&ctl->stats[0], (uint32_t)valid_lanes);
+        atomicAdd(&ctl->stats[1], (uint32_t)valid_lanes);
+        if (bypass) atomicAdd(&ctl->stats[2], 1u);
+        atomicAdd(&ctl->stats[3], 1u);
+      }
+    }
+    return;
+  }
+
+  // 1. box sums: the lane owns window columns x0, x0 + 1 and walks the 80 rows
+  // with a sliding 4-row sum of the packed horizontal 4-sums.
+  {
+    const int x0 = 2 * lane, sh = x0 & 3;
+    const uint8_t* src = buf + (x0 & ~3);
+    uint8_t* dst = pr + sh * FLOW_PRUNE_PLANE + (x0 >> 2);  // planes sh and sh + 1
+    uint32_t h1 = 0, h2 = 0, h3 = 0;
+#pragma unroll 8
+    for (int r = 0; r < K * 5 + B - 1; r++) {
+      const uint32_t* w = reinterpret_cast<const uint32_t*>(src + r * P);
+      const uint32_t w0 = w[0], w1 = w[1];
+      const uint32_t a0 = __builtin_amdgcn_alignbyte(w1, w0, sh);
+      const uint32_t a1 = __builtin_amdgcn_alignbyte(w1, w0, sh + 1);
+      const uint32_t h0 = __builtin_amdgcn_sad_u8(a0, 0u, 0u) | (__builtin_amdgcn_sad_u8(a1, 0u, 0u) << 16);
+      const uint32_t v = h0 + h1 + h2 + h3;  // two sums <= 4080: no carry between the halves
+      h3 = h2; h2 = h1; h1 = h0;
+      if (r >= 3) {
+        dst[(r - 3) * 32] = (uint8_t)((v & 0xFFFFu) >> 4);
+        dst[(r - 3) * 32 + FLOW_PRUNE_PLANE] = (uint8_t)(v >> 20);
+      }
+    }
+    // q of the cur blocks: lane = (block, sub-block row, sub-block column)
+    const uint32_t* cw = cur + ((lane >> 4) * B + 4 * ((lane >> 2) & 3)) * 4 + (lane & 3);
+    uint32_t sum = 0;
+#pragma unroll
+    for (int r = 0; r < 4; r++) sum = __builtin_amdgcn_sad_u8(cw[4 * r], 0u, sum);
+    reinterpret_cast<uint8_t*>(qcur)[lane] = (uint8_t)(sum >> 4);
+#pragma unroll
+    for (int r = 0; r < 5; r++) minlb[64 * r + lane] = ~0u;
+  }
+  lds_fence();
+
+  const int b = lane >> 4;
+  const int dxmin = max(-S, -(it.bx0 + b) * B), dxmax = min(S, p.width - B - (it.bx0 + b) * B);
+  const int Ylo = dymin + S, Yhi = dymax + S;
+  uint32_t qc[4];
+#pragma unroll
+  for (int sy = 0; sy < 4; sy++) qc[sy] = qcur[b * 4 + sy];
+  // 2. bounds: lane = (block, x phase k, 4 dx groups 4m..4m+3); u16 t of a qsad
+  // is the candidate dx + S = 4 (4m + t) + k.
+  {
+    const int k = (lane >> 2) & 3, m = lane & 3;
+    uint32_t mlo = 0, mhi = 0;
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      const int dx = 4 * (4 * m + t) + k - S;
+      const uint32_t msk = (dx < dxmin || dx > dxmax) ? 0xFFFFu : 0u;
+      if (t < 2) mlo |= msk << (16 * t);
+      else mhi |= msk << (16 * (t - 2));
+    }
+    const uint8_t* pl = pr + k * FLOW_PRUNE_PLANE + 4 * b + 4 * m;
+#pragma unroll 1
+    for (int lc = lc0; lc < lc1; lc++) {
+      uint32_t clo = ~0u, chi = ~0u;
+#pragma unroll
+      for (int j = 0; j < K; j++) {
+        // No branch on the row's validity (a scalar mask instead): the chunk
+        // is straight-line code, so the 52 plane reads run ahead of the qsads.
+        // Rows past the valid range are real plane rows (Y <= 64), only masked.
+        const int Y = lc * K + j;
+        const uint32_t my = (Y >= Ylo && Y <= Yhi) ? 0u : ~0u;
+        uint64_t acc = 0;
+#pragma unroll
+        for (int sy = 0; sy < 4; sy++) {
+          const uint32_t* rp = reinterpret_cast<const uint32_t*>(pl + (Y + 4 * sy) * 32);
+          acc = __builtin_amdgcn_qsad_pk_u16_u8(((uint64_t)rp[1] << 32) | rp[0], qc[sy], acc);
+        }
+        clo = pk_min(clo, pk_key((uint32_t)acc, (uint32_t)j) | mlo | my);
+        chi = pk_min(chi, pk_key((uint32_t)(acc >> 32), (uint32_t)j) | mhi | my);
+      }
+#pragma unroll
+      for (int t = 0; t < 4; t++) {
+        const uint32_t e = ((t < 2 ? clo : chi) >> (16 * (t & 1))) & 0xFFFFu;
+        if (e != 0xFFFFu)
+          atomicMin(&minlb[(lc * TB + b) * G + 4 * m + t], ((e >> 4) << 7) | ((e & 15u) << 3) | (uint32_t)k);
+      }
+    }
+    // the fold column dx = +S (plane 0, index 4b + 16 ..): lane = (block, dy mod 16)
+    if (S <= dxmax) {
+#pragma unroll 1
+      for (int rr = 0; rr < 5; rr++) {
+        const int Y = (lane & 15) + 16 * rr;
+        if (Y <= 2 * S && Y >= Ylo && Y <= Yhi) {
+          uint32_t lb = 0;
+#pragma unroll
+          for (int sy = 0; sy < 4; sy++)
+            lb = __builtin_amdgcn_sad_u8(*reinterpret_cast<const uint32_t*>(pr + (Y + 4 * sy) * 32 + 4 * b + 16),
+                                         qc[sy], lb);
+          const int lc = Y / K, j = Y - lc * K;
+          atomicMin(&minlb[(lc * TB + b) * G + j], (lb << 7) | ((uint32_t)j << 3) | 4u);
+        }
+      }
+    }
+  }
+  lds_fence();
+
+  // 3. seeds: lane = (block, block row); e = the block's smallest entry with
+  // its chunk and group appended.
+  {
+    uint32_t e = ~0u;
+    for (int lc = lc0; lc < lc1; lc++) {
+      const uint32_t v = minlb[(lc * TB + b) * G + (lane & 15)];
+      if (v != ~0u) e = min(e, (v << 7) | ((uint32_t)lc << 4) | (uint32_t)(lane & 15));
+    }
+    e = min(e, swz_xor<8>(e));
+    e = min(e, swz_xor<4>(e));
+    e = min(e, swz_xor<2>(e));
+    e = min(e, swz_xor<1>(e));
+#pragma unroll 1
+    for (int sd = 0; sd < 2; sd++) {
+      bool ok = b < it.nb;
+      int Y = S, X = S;
+      asm volatile("" : "+v"(Y), "+v"(X));  // no constant key words kept live in VGPRs
+      if (sd == 1) {
+        ok = ok && e != ~0u;
+        const uint32_t ent = e >> 7;
+        const int kk = (int)(ent & 7u);
+        if (ok) {
+          Y = K * (int)((e >> 4) & 7u) + (int)((ent >> 3) & 15u);
+          X = kk == 4 ? 2 * S : 4 * (int)(e & 15u) + kk;
+        }
+      }
+      const int y = lane & 15;
+      const int off = (Y + y) * P + b * B + X;
+      const uint32_t* w = reinterpret_cast<const uint32_t*>(buf + (off & ~3));
+      const uint32_t* c = cur + (b * B + y) * 4;
+      uint32_t sad = 0;
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w[i + 1], w[i], off & 3), c[i], sad);
+      sad += swz_xor<8>(sad);
+      sad += swz_xor<4>(sad);
+      sad += swz_xor<2>(sad);
+      sad += swz_xor<1>(sad);
+      if (ok && y == 0)
+        atomicMin(reinterpret_cast<unsigned long long*>(&keys[b]),
+                  (unsigned long long)make_key(sad, X - S, Y - S));
+    }
+  }
+  lds_fence();
+
+  // 4. the live list (the planes are dead: the list overlays them)
+  int L = 0;
+  const uint32_t magic_nb = 0xFFFFFFFFu / (uint32_t)it.nb + 1u;
+  for (int r = 0; r < nw; r++) {
+    const int idx = 64 * r + lane;
+    const bool valid = idx < valid_lanes;
+    const int ii = valid ? idx : 0;
+    const int bg = ii >> 4, gi = ii & 15;
+    const int lcr = it.nb == 1 ? bg : (int)__umulhi((uint32_t)bg, magic_nb);
+    const int b2 = bg - lcr * it.nb;
+    const uint32_t v = minlb[((lc0 + lcr) * TB + b2) * G + gi];
+    const int U = (int)(uint32_t)(keys[b2] >> 32);
+    const bool live = valid && v != ~0u && 16 * (int)(v >> 7) - 240 <= U;
+    if (verify) {
+      if (valid) {
+        list[idx] = (uint16_t)idx;
+        dead[idx] = live ? 0 : 1;
+      }
+      if (r == 0 && lane < TB) ub[lane] = (uint32_t)(keys[lane] >> 32);
+    }
+    const uint64_t bal = __builtin_amdgcn_ballot_w64(live);
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
+                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    if (live && !verify) list[L + rank] = (uint16_t)idx;
+    L += (int)__builtin_popcountll(bal);
+  }
+  if (lane == 0) {
+    ctl->live[slot] = (uint32_t)(verify ? valid_lanes : L);
+    // (bound phases of several slots run at once: an add, not a store of run + 1)
+    if (pf & PF_BYPASS) {
+      if (4 * L > 3 * valid_lanes) {
+        if (!prober) __hip_atomic_fetch_add(&ctl->run, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      } else
+        __hip_atomic_store(&ctl->run, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    if (stats) {
+      atomicAdd(&ctl->stats[0], (uint32_t)L);
+      atomicAdd(&ctl->stats[1], (uint32_t)valid_lanes);
+      atomicAdd(&ctl->stats[3], 1u);
+    }
+  }
+}
+
 template <int B, int K, int PC>
 __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g, FlowJobs jb) {
   static_assert(B == 16, "cur-block DMA layout of stage_item_wave");
   constexpr int CW = B / 4;
   extern __shared__ __align__(16) uint8_t smem[];
-  const int NB = g.flow_slots;
-  const int slot_bytes = g.tile_bytes + g.tb * B * B;
+  // Pruning (flow_bound above) is compiled into the 144-byte-pitch instance
+  // only: the planner turns it on for no other shape.
+  const bool prune = PC == 144 && g.prune != 0;
+  const int NB = prune ? g.prune_slots : g.flow_slots;
+  const int slot_bytes = g.tile_bytes + g.tb * B * B + (prune ? FLOW_PRUNE_BYTES : 0);
   uint64_t* keys = reinterpret_cast<uint64_t*>(smem + NB * slot_bytes);  // [NB][tb]
   FlowCtl* ctl = reinterpret_cast<FlowCtl*>(smem + NB * slot_bytes + NB * g.tb * 8);
   const int tid = (int)threadIdx.x, lane = tid & 63;
@@ -1037,6 +1335,14 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     if (tid < 16) {
       ctl->ready[tid] = 0;
       ctl->done[tid] = 0;
+      if (prune) ctl->live[tid] = 0;
+    }
+    if (prune && tid >= 32 && tid < 36) ctl->stats[tid - 32] = 0;
+    if (tid == 16) {
+      ctl->run = 0;
+      ctl->pflags = !prune ? 0u
+                           : (uint32_t)(PF_ON | (g.prune == 2 ? PF_VERIFY : 0) | (g.prune_bypass ? PF_BYPASS : 0) |
+                                        (g.prune_stats ? PF_STATS : 0));
     }
   }
   for (int i = tid; i < NB * g.tb; i += (int)blockDim.x) keys[i] = ~0ull;
@@ -1050,9 +1356,14 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     // profiles/r02ae_ab_flow_start.txt).
     for (int i = 0; i < wave; i++) __builtin_amdgcn_s_sleep(10);
     if (g.prio) __builtin_amdgcn_s_setprio(3);  // see me_fast_kernel
-    stage_item_wave<B>(p, g, flow_item<B, K>(p, g, jb, tile_of(wave)), smem + wave * slot_bytes, jb);
+    const Item it0 = flow_item<B, K>(p, g, jb, tile_of(wave));
+    stage_item_wave<B>(p, g, it0, smem + wave * slot_bytes, jb);
     if (g.prio) __builtin_amdgcn_s_setprio(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (PC == 144) {
+      if (prune)
+        flow_bound<B, K>(p, g, it0, smem + wave * slot_bytes, keys + wave * g.tb, ctl, wave);
+    }
     if (lane == 0)
       __hip_atomic_store(&ctl->ready[wave], (uint32_t)wave + 1u, __ATOMIC_RELEASE,
                          __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1067,8 +1378,10 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
   const int fw = bid * 16 + wave;
   unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_first = 0, st_spin = 0, st_n = 0;
   const unsigned long long st_r0 = __builtin_amdgcn_s_memrealtime();
+  unsigned long long st_dma = 0, st_bound = 0, st_nb = 0;  // refills: DMA wait, bound phase, count
 #endif
   for (;;) {
+    const int pfl = PC == 144 ? __builtin_amdgcn_readfirstlane((int)ctl->pflags) : 0;
     uint32_t q = 0;
     if (lane == 0) q = __hip_atomic_fetch_add(&ctl->next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
@@ -1120,13 +1433,16 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     const uint32_t tile_off = (uint32_t)(slot * slot_bytes);
     const int G = g.groups;
     const int t = (int)q - basec;
-    const int i = 64 * t + lane;
-    const int T = nwc * 64;  // lanes past the item's tasks are masked below
     const int dymin = max(-S, -it.tly), dymax = min(S, p.height - it.h - it.tly);
     const int lc1 = min(it.nch, (dymax + S) / K + 1);
     const int valid_lanes = (lc1 - lc0c) * it.nb * G;
-    const bool live = i < valid_lanes;
-    (void)T;
+    // Pruning: task t takes the item's live lane-tasks [64 t, 64 t + 64) of the
+    // slot's list; a task past the list only counts itself done.
+    const int nlive = pfl ? __builtin_amdgcn_readfirstlane((int)ctl->live[slot]) : valid_lanes;
+    if (64 * t < nlive) {
+    const bool live = 64 * t + lane < nlive;
+    const uint16_t* llist = reinterpret_cast<const uint16_t*>(buf + g.tile_bytes + g.tb * B * B);
+    const int i = pfl && live ? (int)llist[64 * t + lane] : 64 * t + lane;
     const int ii = live ? i : 0;
     const int bg = (int)__umulhi((uint32_t)ii, g.magic_groups);  // ii / G
     const int gi = ii - bg * G;
@@ -1220,6 +1536,16 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       atomicMin(reinterpret_cast<unsigned long long*>(&keys[slot * g.tb + b]),
                 (unsigned long long)make_key(best >> 16, dx, dy));
     }
+    if constexpr (PC == 144) {
+      // Verify mode: a lane-task the bound marked dead must hold no candidate
+      // with SAD <= its block's U_b.
+      if ((pfl & PF_VERIFY) && live && best < 0xFFFF0000u) {
+        const uint8_t* pv = buf + g.tile_bytes + g.tb * B * B;
+        if (pv[640 + i] && (best >> 16) <= reinterpret_cast<const uint32_t*>(pv + 960)[b] && p.sched)
+          __hip_atomic_store(p.sched + SCHED_ERR, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    }
     // this wave-task is done; the last one of the item writes and refills the slot
     uint32_t prev = 0;
     if (lane == 0)
@@ -1228,7 +1554,9 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     if ((int)prev + 1 == nwc) {
       if (lane < it.nb) {
         const uint64_t kk = keys[slot * g.tb + lane];
-        keys[slot * g.tb + lane] = ~0ull;
+        uint64_t none = ~0ull;  // materialised here, not kept live (it spilled)
+        asm volatile("" : "+v"(none));
+        keys[slot * g.tb + lane] = none;
         const int out = (it.by - jb.r0[it.j]) * p.nbx + it.bx0 + lane;
         int16_t* mv = jb.mv[it.j];
         store_mv(mv, out, kk);
@@ -1238,13 +1566,40 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       const int kn = kc + NB;
       if (kn < nitems) {
         if (g.prio) __builtin_amdgcn_s_setprio(3);
-        stage_item_wave<B>(p, g, flow_item<B, K>(p, g, jb, tile_of(kn)), buf, jb);
+        const Item itn = flow_item<B, K>(p, g, jb, tile_of(kn));
+#ifdef ME_STAMPS
+        const unsigned long long st_d0 = __builtin_amdgcn_s_memtime();
+#endif
+        stage_item_wave<B>(p, g, itn, buf, jb);
         if (g.prio) __builtin_amdgcn_s_setprio(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef ME_STAMPS
+        const unsigned long long st_d1 = __builtin_amdgcn_s_memtime();
+        st_dma += st_d1 - st_d0;
+#endif
+        if constexpr (PC == 144) {
+          // (at raised issue priority: nothing of the item runs before its bound ends)
+          if (pfl) {
+            __builtin_amdgcn_s_setprio(3);
+            flow_bound<B, K>(p, g, itn, buf, keys + slot * g.tb, ctl, slot);
+            __builtin_amdgcn_s_setprio(0);
+          }
+        }
+#ifdef ME_STAMPS
+        st_bound += __builtin_amdgcn_s_memtime() - st_d1;
+        st_nb++;
+#endif
         if (lane == 0)
           __hip_atomic_store(&ctl->ready[slot], (uint32_t)kn + 1u, __ATOMIC_RELEASE,
                              __HIP_MEMORY_SCOPE_WORKGROUP);
       }
+    }
+  }
+  if constexpr (PC == 144) {
+    // Tuning build: this workgroup's counts, once every wave is out of the loop.
+    if ((__builtin_amdgcn_readfirstlane((int)ctl->pflags) & PF_STATS) && p.sched) {
+      __syncthreads();
+      if (tid < 4) atomicAdd(p.sched + SCHED_PRUNE + tid, ctl->stats[tid]);
     }
   }
 #ifdef ME_STAMPS
@@ -1254,6 +1609,9 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     unsigned long long* o = g_stamps + 8 * fw;
     o[0] = st_t0; o[1] = st_first; o[2] = __builtin_amdgcn_s_memtime(); o[3] = st_spin;
     o[4] = st_n; o[5] = st_r0; o[6] = __builtin_amdgcn_s_memrealtime(); o[7] = hw;
+    if (fw < (1 << 14)) {  // per wave, refills: [DMA wait cycles, bound cycles, refills]
+      g_wstamps[8 * fw] = st_dma; g_wstamps[8 * fw + 1] = st_bound; g_wstamps[8 * fw + 2] = st_nb;
+    }
   }
 #endif
 }
@@ -1460,9 +1818,10 @@ static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const Sear
   // the ds_read2 offsets); any other pitch takes the runtime-pitch body
 #define ME_FLOW_CASE(PP)                                                                        \
   if (PP == 0 || g.pitch == PP) {                                                               \
-    const hipError_t e = lds_attr((const void*)me_flow_kernel<16, 13, PP>, g.lds);              \
+    const int lds = PP == 144 && g.prune ? g.prune_lds : g.lds;                                 \
+    const hipError_t e = lds_attr((const void*)me_flow_kernel<16, 13, PP>, lds);                \
     if (e != hipSuccess) return e;                                                              \
-    hipLaunchKernelGGL((me_flow_kernel<16, 13, PP>), dim3((unsigned)nwg), dim3(1024), g.lds,    \
+    hipLaunchKernelGGL((me_flow_kernel<16, 13, PP>), dim3((unsigned)nwg), dim3(1024), lds,      \
                        stream, p, g, jb);                                                       \
     return hipGetLastError();                                                                   \
   }

@@ -36,6 +36,11 @@ struct Tuning {
   int fair = -1;          // ME_FAIR=0..3: flow-kernel waves behind the pull counter raise their priority: 0 off, 1 in launches
                           // with refills (automatic), 2 on items whose slot gets a refill, 3 always
   int fair_lo = 8, fair_hi = 16;  // ME_FAIR_T=lo,hi: the lags (pulls) that raise a wave to priority 1 / 2
+  int prune = -1;         // ME_PRUNE=0|1|2: flow-kernel candidate pruning off / on / verify (every lane-task runs; a
+                          // lane-task the bound marked dead that holds a candidate with SAD <= its block's seed
+                          // cost sets the error word) (-1 = automatic: on)
+  int prune_bypass = -1;  // ME_PRUNE_BYPASS=0|1: skip the bound after a run of items it could not thin (-1 = automatic: on)
+  int prune_stats = 0;    // set by the tuning build: the flow kernel counts live / total lane-tasks and bypassed items
   int flow_one = -1;      // ME_FLOW_ONE=0|1: a batch's flow jobs in launches of one ring / in one launch (-1 = automatic: one)
   int mfma_s2k = -1;      // ME_MFMA_S2K=0|1: 16x16 SSD, S <= 64: S2 from the prepass plane / formed in
                           // the workgroup (-1 = automatic: the kernel path, ME_PATH_MFMA_LEAN)

@@ -362,7 +362,26 @@ bool plan_flow(const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g) {
   q.fair = tu.fair != 0 ? (tu.fair_lo | tu.fair_hi << 8 | (tu.fair > 1 ? tu.fair : 1) << 16) : 0;
   q.strip_w = 0;
   q.lds = best_ns * slot + best_ns * q.tb * 8 + (int)sizeof(int) * 40;
-  return q.lds <= FLOW_LDS_BUDGET;
+  if (q.lds > FLOW_LDS_BUDGET) return false;
+  // Candidate pruning (the kernel's flow_bound): the shape the bound phase is
+  // written for (4 blocks, 16 dx groups, 5 chunks, the compiled 144-byte
+  // pitch); every ring slot carries its own bound scratch, so as many bound
+  // phases run at once as slots are being refilled and none waits for scratch.
+  // A slot grows from 12,544 to 23,744 bytes: 6 slots where 12 fitted.
+  if (tu.prune != 0 && q.tb == 4 && G == 16 && chunks == 5 && q.pitch == 144) {
+    const int pslot = slot + FLOW_PRUNE_BYTES;
+    int ns = (FLOW_LDS - 16 * q.tb * 8 - FLOW_CTL_BYTES) / pslot;
+    if (ns > 16) ns = 16;
+    if (tu.flow_slots && tu.flow_slots < ns) ns = tu.flow_slots;
+    if (ns >= 2) {
+      q.prune = tu.prune == 2 ? 2 : 1;
+      q.prune_bypass = tu.prune_bypass != 0;
+      q.prune_stats = tu.prune_stats;
+      q.prune_slots = ns;
+      q.prune_lds = ns * pslot + ns * q.tb * 8 + FLOW_CTL_BYTES;
+    }
+  }
+  return true;
 }
 
 }  // namespace me

@@ -102,3 +102,14 @@ for x in range(8):
     sx = np.isin(wg, np.unique(wg)[xcd == x])
     print(f"  XCD {x}: clock {np.median(clk[sx]):.3f} GHz, CU end median {np.median(cu_e[xcd == x]) / 100:.2f} "
           f"max {cu_e[xcd == x].max() / 100:.2f} us, tasks {ntask[sx].sum()}")
+
+# Pruning launches: what a slot's refill costs the wave that does it (per
+# refill, shader cycles): the wait for the item's DMA and the bound phase.
+L.me_debug_wave_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
+wbuf = np.zeros(8 << 14, np.uint64)
+L.me_debug_wave_stamps(wbuf.ctypes.data, wbuf.size)
+ws = wbuf.reshape(-1, 8)[:4096].astype(np.int64)
+nref = ws[:, 2].sum()
+if nref:
+    print(f"refills {nref}: DMA wait mean {ws[:, 0].sum() / nref:.0f} cycles, stage-to-publish after it "
+          f"(bound phase) mean {ws[:, 1].sum() / nref:.0f} cycles; spin per task mean {spin.sum() / max(ntask.sum(), 1):.0f}")
