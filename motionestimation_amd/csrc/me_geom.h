@@ -81,7 +81,7 @@ struct QsadGeom {
                    // strip top to bottom (wide frames: an XCD's L2 keeps the strip's
                    // window rows while the tile rows that read them pass)
   int nbx_full;    // full-width blocks per row
-  int aligned;     // 4-byte aligned global rows
+  int aligned;     // 4-byte aligned global rows and W % 4 == 0: staged by LDS DMA
   int tile16;      // ref tile staged in 16-byte granules (X0, width, rows 16-byte aligned)
   int fold;        // SAD, S % 4 == 0: groups = S/2 cover dx in [-S, S-1]; the dx = +S
                    // column is spread over lanes gi < K, one v_sad_u8 candidate each

@@ -228,7 +228,12 @@ bool plan_fast(const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g, int* 
                 (uint32_t)g->wg_per_row * (uint32_t)(rows > 0 ? rows : 1)))
     g->magic_wpr = 0;
   g->magic_tb = magic((uint32_t)g->tb);
-  g->aligned = (s.align & ALIGN_4) != 0;
+  // The DMA path stages 4-byte granules under the planes' range check, which
+  // ends W bytes into the last resident row: with W % 4 != 0 the granule
+  // holding that row's last pixels straddles the end and comes back all zero
+  // (334 x 51 at a pitch of 336: SADs of candidates on the last row's last two
+  // columns too large).  Such frames take the byte-copy staging.
+  g->aligned = (s.align & ALIGN_4) != 0 && s.width % 4 == 0;
   // X0 = tb*B*t - S - a is 16-aligned for every tile when a = 0 (S % 4 == 0),
   // S % 16 == 0 and tb * B % 16 == 0; rows of the ref plane 16-aligned; W % 16
   // == 0 keeps the last in-frame granule of the last row inside the range.

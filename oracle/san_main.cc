@@ -197,6 +197,9 @@ static void check_plan(const me::PlanShape& s, const me::QsadGeom& g, int K, boo
     CHECK(g.lds <= me::QSAD_LDS_BUDGET + 16);
     CHECK(g.flow_slots == 0);
     CHECK(!g.tile16 || g.aligned);
+    // DMA staging: no 4-byte granule may straddle the end of a frame row (the
+    // range check would zero the last resident row's last pixels)
+    CHECK(!g.aligned || s.width % 4 == 0);
   }
 }
 
