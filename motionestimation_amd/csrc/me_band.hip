@@ -61,7 +61,6 @@
 
 #include "me_kernels.h"
 #include "me_mfma_util.h"
-#include "me_tuning.h"
 
 namespace me {
 
@@ -72,10 +71,9 @@ using mfma::mfma_job;
 using mfma::opaque;
 using mfma::umin3;
 
+// (BW_CREC, BW_NSW, BW_PW, BW_K, BW_WIN_ROWS, BwCtl and the LDS layout helpers
+// the planner shares with the kernel: me_mfma_geom.h)
 constexpr int BW_OPS = 46;           // producer steps per band: 16 rows in, then 15 x (out, in)
-constexpr int BW_CREC = 48;          // cur row record: 16 zero bytes, the row (c ^ 0x7F), 16 zero bytes
-constexpr int BW_NSW = 12;           // searcher waves per workgroup (three per SIMD)
-constexpr int BW_PW = 4;             // producer waves per workgroup (one per SIMD)
 
 #ifdef ME_STAMPS
 // Diagnostic build only (libme_hip_stamps.so): per workgroup and wave, the
@@ -94,22 +92,6 @@ __device__ unsigned long long g_bwtimes[BW_STW * 2 * 4096];
 #define BW_ACC(k) do { } while (0)
 #endif
 
-constexpr int BW_K = 8;              // band ring: the bands in flight (window + P0 plane each)
-
-constexpr int BW_WIN_ROWS = 31;      // window rows of a band: 16 b .. 16 b + 30
-
-// Producer -> searcher handshake per band slot (LDS): ready[k] = the band
-// whose window and P0 plane slot k holds (published after they are written);
-// done[k] = searcher waves finished with it (the producer of band b + K
-// waits for all of them, then reuses the slot).
-struct BwCtl {
-  uint32_t trash[4];  // (16-byte aligned) the P0 store of producer lanes without an output
-  int ready[BW_K];
-  int done[BW_K];
-  int hbready[BW_K];  // the partial row's plane of band lo_h + i formed
-  int hbcnt[BW_K];    // the partial row's bands searched, per block column
-};
-
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const uint32_t lds_c32;
 typedef __attribute__((address_space(3))) const v4i lds_cv4i;
@@ -122,20 +104,6 @@ __device__ __forceinline__ uint32_t ld32(uint32_t a) {
 }
 __device__ __forceinline__ v4i ldv4(uint32_t a) {
   return *reinterpret_cast<lds_cv4i*>((uintptr_t)a);
-}
-
-// LDS layout (bytes): K windows | K P0 planes | crec (searchers) | staged cur
-// rows (searchers) | keys | ctl
-__host__ __device__ constexpr int bw_win(int lp) { return BW_WIN_ROWS * lp; }
-__host__ __device__ inline int bw_lds_bytes(int lp, int pp, int ns, int nsw) {
-  return BW_K * bw_win(lp) + BW_K * 16 * pp * 4 + nsw * 16 * BW_CREC + nsw * 256 + nsw * ns * 8 +
-         (int)sizeof(BwCtl);
-}
-// the partial bottom row's extra LDS: its nhb S2 planes and a key per block
-// column of the strip
-__host__ __device__ inline int bw_lds_hb_bytes(int pp, int ns, int nhb) {
-  (void)ns;
-  return nhb ? nhb * 16 * pp * 4 + BW_K * 8 : 0;  // its planes, a key per block column
 }
 
 // Bounded spin on an LDS word (the handshake's ordering argument says it
@@ -168,20 +136,11 @@ __device__ __forceinline__ bool bw_wait(const SearchArgs& p, int lane, Pred ok) 
 // (kx = items mod CUs per XCD) are cut into st segments each so that round
 // fills the XCD's CUs too (a whole strip item takes rows + 2 ceil(S/16) + 2
 // band times; its st segments ~ rows / st + that).  Launch order within an
-// XCD is blockIdx order, so the segments run last.
+// XCD is blockIdx order, so the segments run last.  (bw_xcd_split and the
+// launch's grid, bw_xt_grid: me_mfma_geom.h)
 struct BwItem {
   int u, seg, rows;  // segment seg of item u: block rows [seg rows, + rows), clipped to the job's
 };
-__host__ __device__ inline void bw_xcd_split(int nx, int cx, int rows, int* main, int* kx, int* st,
-                                             int* L) {
-  int k = nx % cx, s = 1;
-  if (k) s = max(1, min(cx / k, rows / 4));
-  const int l = (rows + s - 1) / s;
-  *kx = k;
-  *L = l;
-  *st = (rows + l - 1) / l;
-  *main = nx - k;
-}
 __device__ __forceinline__ BwItem bw_item(const MfmaGeom& g, int jobs) {
   if (!g.bw_xt) {
     int lin = mfma::xcd_banded_index();
@@ -890,134 +849,15 @@ __global__ __launch_bounds__(64 * (NSW + PW), 4) void me_mfma_bw_kernel(SearchAr
 #endif
 }
 
-// Smallest pitch >= need with pitch = r (mod m): the conflict-free classes of
-// the tiles' ds_read_b128 lane groups (window LP = 32 mod 64 bytes, P0 PP = 8
-// mod 16 ints; checked for every group of 16 lanes).
-static int pitch_at_least(int need, int r, int m) {
-  int p = need + ((r - need) % m + m) % m;
-  return p;
-}
-
 }  // namespace
-
-bool plan_bw(const SearchArgs& p, MfmaGeom* g, int jobs) {
-  const int S = p.range;
-  g->bw = 0;
-  if (p.blk != 16 || S < 1 || S > 64 || tuning().bw == 0) return false;
-  if (p.stride % 16 || (uintptr_t)p.cur % 16) return false;  // 16-byte cur row loads
-  const int rows = g->nrows - (g->hb_row >= 0 ? 1 : 0);       // full-height rows
-  if (rows < 1 || g->nbx < 1) return false;
-  // Two ring slots per searcher wave (A fragments of 2 rows: 64 VGPRs): the
-  // 2 ceil(S/16) + 1 rows in flight of a column split over 12 / C searchers,
-  // the widest strip whose column fits its rows: S <= 16: 6 columns (3 rows
-  // on 4 slots); S <= 32: 4 (5 on 6); S <= 48: 3 (7 on 8); S <= 64: 2 (9 on
-  // 12).  One workgroup of 12 searchers + 4 producers per CU (four waves per
-  // SIMD at <= 128 VGPRs).
-  const int nsw = BW_NSW, npw = BW_PW, ns = 2, wgs_cu = 1;
-  const int inflight = 2 * ((S + 15) / 16) + 1;
-  int C = 0;
-  for (int c : {6, 4, 3, 2, 1})
-    if (nsw % c == 0 && (nsw / c) * ns >= inflight) {
-      C = c;
-      break;
-    }
-  if (C == 0) return false;
-  const int npos_max = 16 * ((16 * (C - 1) + 2 * S) / 16 + 2);
-  const int lp = npos_max + 16 <= 160 ? 160 : 224;
-  if (npos_max + 16 > lp || npos_max / 4 > 52) return false;  // 4 lane rows x 13 output groups
-  const int pp = pitch_at_least(npos_max, 8, 16);
-  g->bw_wpc = nsw / C;
-  g->bw_ns = ns;
-  g->bw_nsw = nsw;
-  g->bw_pw = npw;
-  g->bw_cols = C;
-  g->bw_lp = lp;
-  g->bw_pp = pp;
-  g->bw_strips = (g->nbx + C - 1) / C;
-  // Segments: rounds of resident workgroups x (the most bands one segment
-  // walks + ~2 bands of prologue), the smallest.  A segment of rows [r0, r1)
-  // walks bands lo(r0) .. hi(r1 - 1); even splits, the last segment the
-  // rest.  (Uneven splits -- a longer first segment, which walks ceil(S/16)
-  // fewer bands, the partial row's segment shorter -- measured 1.5 % slower
-  // at 1080p: profiles/r06g_bw_ab.jsonl; longer first and last segments with
-  // shorter middle ones, 12 bands worst instead of 13 at 1080p one frame,
-  // 1.5 % slower again: 38.6 against 38.0 us per call, r06zl_bw_seg.jsonl.
-  // The segments' band counts do not set the time alone.)
-  const int cus = cu_count() * wgs_cu;
-  const int nfull = g->row0 + rows;  // (rows from row0: the job's full-height rows)
-  auto lo_b = [&](int br) { return std::max(16 * br - S, 0) >> 4; };
-  auto hi_b = [&](int br) { return std::min(16 * br + S, p.height - 16) >> 4; };
-  const long per = (long)std::max(jobs, 1) * g->bw_strips;
-  long best_t = 1L << 40;
-  int best_l = rows, best_segs = 1;
-  for (int segs = 1; segs <= std::max(1, rows / 4); segs++) {
-    const int L = (rows + segs - 1) / segs;
-    if ((rows + L - 1) / L != segs) continue;  // (an empty last segment)
-    const long rounds = (per * segs + cus - 1) / cus;
-    int worst = 0;  // bands of the longest segment
-    for (int r0 = g->row0; r0 < nfull; r0 += L)
-      worst = std::max(worst, hi_b(std::min(r0 + L, nfull) - 1) - lo_b(r0) + 1);
-    const long t = rounds * (worst + 2);
-    if (t < best_t) {
-      best_t = t;
-      best_l = L;
-      best_segs = segs;
-    }
-  }
-  if (tuning().bw_seg > 0) {
-    best_l = std::min(rows, tuning().bw_seg);
-    best_segs = (rows + best_l - 1) / best_l;
-  }
-  g->bw_seg_rows = best_l;
-  g->bw_abl = tuning().bw_abl;
-  g->bw_segs = best_segs;
-  // Launches of whole rounds of strips take the per-XCD tail split instead.
-  g->bw_xt = 0;
-  g->bw_cx = cu_count() / 8;
-  if (tuning().bw_xt != 0 && tuning().bw_seg == 0 && per >= cus && g->bw_cx > 0) {
-    g->bw_xt = 1;
-    g->bw_seg_rows = rows;
-    g->bw_segs = 1;
-  }
-  g->lds = bw_lds_bytes(lp, pp, ns, nsw);
-  if (g->lds > 160 * 1024 / wgs_cu) return false;
-  // A partial bottom block row (rows H - hb .. H - 1) joins the walk when its
-  // hb-row S2 planes fit in LDS beside the ring: one per band it meets, bands
-  // lo .. hb_row (its last candidate row is H - hb = 16 hb_row); otherwise it
-  // is a second launch of the lean kernel (launch_bw_jobs).
-  g->bw_hb = 0;
-  if (g->hb_row >= 0 && tuning().bw_hb != 0) {
-    const int nhb = g->hb_row - (std::max(16 * g->hb_row - S, 0) >> 4) + 1;
-    const int lds_hb = g->lds + bw_lds_hb_bytes(pp, ns, nhb);
-    if (lds_hb <= 160 * 1024 / wgs_cu) {
-      g->bw_hb = nhb;
-      g->lds = lds_hb;
-    }
-  }
-  g->bw = 1;
-  return true;
-}
-
-bool bw_one_round(const MfmaGeom& g, int jobs) {
-  return (long)std::max(jobs, 1) * g.bw_strips * g.bw_segs <= (long)cu_count();
-}
 
 hipError_t launch_bw(const SearchArgs& p, const MfmaGeom& g0, const MfmaJobs& jb0, hipStream_t stream) {
   MfmaGeom g = g0;
   g.nrows = g0.nrows - (g0.hb_row >= 0 ? 1 : 0);  // full-height rows: the kernel's
   MfmaJobs jb = jb0;
   jb.wgs = g.bw_strips * g.bw_segs;
-  long wgs = (long)jb.n * jb.wgs;
-  if (g.bw_xt) {  // 8 XCDs x the most slots one of them needs (bw_item)
-    const long per = (long)jb.n * g.bw_strips;
-    int wmax = 0;
-    for (int nx : {(int)(per / 8), (int)((per + 7) / 8)}) {
-      int mainx, kx, st, L;
-      bw_xcd_split(nx, g.bw_cx, g.bw_seg_rows, &mainx, &kx, &st, &L);
-      wmax = std::max(wmax, mainx + kx * st);
-    }
-    wgs = 8L * wmax;
-  }
+  const long wgs = g.bw_xt ? bw_xt_grid((long)jb.n * g.bw_strips, g.bw_cx, g.bw_seg_rows)
+                           : (long)jb.n * jb.wgs;
   const dim3 grid((unsigned)wgs), blk(64 * (g.bw_nsw + g.bw_pw));
   hipError_t e;
   // ablation instances (tuning build only: ME_BW_ABL) are separate kernels

@@ -51,12 +51,8 @@
 #include "me_mfma_util.h"
 #include "me_tuning.h"
 
-// Steps between a row's last MFMA and its epilogue (the 16-register accumulator
-// ring holds 13 + DLY rows); 2 and 3 measured slower (DESIGN.md, 8x8 blocks).
-constexpr int MFMA_DLY = 1;
-#ifndef ME_SSD8_KM
-#define ME_SSD8_KM 3  // 8x8 chunk length L = 16 KM: 48 rows (8K +-128: 64 rows 7.12 ms, 48 6.95-7.0, 32 8.3)
-#endif
+// (MFMA_DLY, ME_SSD8_KM / NT / WP and the LDS layout constants the planners
+// share with the kernels: me_mfma_geom.h)
 #ifndef SSD8_STRIP
 #define SSD8_STRIP 32  // 8x8 kernel: tile columns per strip of the workgroup order (1,024 pixels)
 #endif
@@ -66,14 +62,8 @@ constexpr int MFMA_DLY = 1;
 #ifndef ME_SSD8_WPE
 #define ME_SSD8_WPE 4  // 8x8: waves per SIMD the register budget targets (<= 128 VGPRs)
 #endif
-#ifndef ME_SSD8_NT
-#define ME_SSD8_NT 2  // 8x8: horizontally adjacent 4x4-block tiles per workgroup (1 or 2)
-#endif
 #ifndef ME_SSD8_S2PERM
 #define ME_SSD8_S2PERM 1  // 8x8: S2 table rows permuted in LDS (bank-conflict-free reads)
-#endif
-#ifndef ME_SSD8_WP
-#define ME_SSD8_WP 80  // 8x8 window copy pitch: 4 x (L + 8 = 56) x 80 + S2 table (L + 1) x 256 = 30 KB at L = 48
 #endif
 
 namespace me {
@@ -1021,10 +1011,7 @@ __attribute__((amdgpu_waves_per_eu(ME_SSD8_WPE))) void me_mfma_ssd8_kernel(Searc
 // then dy, then dx (the raster-first rule); the lanes meet in a 64-bit LDS min.
 // Window row pitch LP = 288 (S <= 64) or 544 (S <= 192): LP = 32 (mod 256) puts
 // the 16-byte slots 2n + (h & 1) (mod 16) of a ds_read_b128 lane group on
-// distinct banks.
-constexpr int BM_CREC = 48;   // cur row record: 16 zero bytes, the row (c ^ 0x7F), 16 zero bytes
-constexpr int BM_HDR = 8 * 16 * BM_CREC + 8 * 8 + 8 * 4;  // records, keys, cc
-
+// distinct banks.  (BM_CREC, BM_HDR: me_mfma_geom.h)
 template <int LP>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(4))) void me_mfma_bm16_kernel(SearchArgs p, MfmaGeom g, MfmaJobs jb) {
@@ -1365,9 +1352,7 @@ __attribute__((amdgpu_waves_per_eu(4))) void me_mfma_bm16_kernel(SearchArgs p, M
 // The tiles then read S2 from LDS instead of the plane.  crec (the cur row
 // records) aliases the S2 plane: the A fragments are built before band 0.
 // S <= 64 (window pitch 288): LDS 35 KB, four workgroups per CU as before.
-constexpr int BMV_NP = 268;                // S2 / V plane row pitch (ints): 256 positions + 12 V; 67 * 4
-constexpr int BMV_PLANE = 16 * BMV_NP * 4; // 17,152 bytes (>= the 6,144 of crec)
-constexpr int BMV_LP = 288;
+// (BMV_NP, BMV_PLANE, BMV_LP, bmv_lds<R>(): me_mfma_geom.h)
 // acc + sum over the 4 bytes r of v of (r - 127)^2: u = r ^ 0x7F is 127 - r as
 // an i8 (r in [0, 255] -> u in [-128, 127]), and u^2 = (r - 127)^2
 __device__ __forceinline__ int h4acc(uint32_t v, int acc) {
@@ -1434,11 +1419,6 @@ __device__ __forceinline__ void bmv_vsum_hb(const uint8_t* win, int p, int hb, i
 // and masks the rows of a band that leave it (bit 31 of the key).  A partial
 // bottom block row (height hb) reads a second S2 plane of hb-row sums when it
 // shares the workgroup with a full row.
-template <int R>
-constexpr int bmv_lds() {
-  return R * (8 * 8 + 8 * 4) + (R == 2 ? 2 : 1) * BMV_PLANE + 2 * 31 * BMV_LP;
-}
-
 template <int R>
 __global__ __launch_bounds__(256 * R)
 __attribute__((amdgpu_waves_per_eu(4))) void me_mfma_bmv_kernel(SearchArgs p, MfmaGeom g, MfmaJobs jb) {
@@ -1803,219 +1783,42 @@ __attribute__((amdgpu_waves_per_eu(4))) void me_mfma_bmv_kernel(SearchArgs p, Mf
 
 }  // namespace
 
+// ---- the planners' wrappers (me_mfma_plan.cpp plans; these read the process
+// state once and bind the device pointers) ----
+
 // Process-wide path switch (me_set_kernel_path / ME_PATH, me_tuning.h).
 bool mfma_disabled() { return kernel_path() == 1; }
 
-// Tiles of a B = 16 search over block rows [begin, end) (the merge buffers' size).
-size_t mfma_merge_tiles(const SearchArgs& p) {
-  if (p.blk != 16 || p.width < p.blk) return 0;  // 8x8: no cross-workgroup merge
-  const size_t tx = (size_t)((p.width / p.blk + 3) / 4);
-  const size_t ty = (size_t)((p.block_row_end - p.block_row_begin + 3) / 4);
-  return tx * ty;
+static MfmaShape shape_of(const SearchArgs& p) {
+  return {p.width, p.height, p.stride, p.blk, p.range, p.cost_kind, p.block_row_begin,
+          p.block_row_end, p.nbx, align_class(p.stride, p.ref, p.cur),
+          p.mkeys && p.mcnt ? p.merge_tiles : 0};
+}
+
+// The plan's pointers: the prepass planes in p's scratch (null without
+// scratch or for a plan without planes) and the merge buffers.
+static void bind(const SearchArgs& p, MfmaGeom* g) {
+  uint8_t* s = g->scratch_bytes ? p.scratch : nullptr;
+  uint8_t* s2 = s ? s + (((size_t)g->rp_bytes + 255) & ~(size_t)255) : nullptr;
+  g->rp = g->rp_bytes ? reinterpret_cast<int8_t*>(s) : nullptr;
+  g->s2 = reinterpret_cast<int*>(s2);
+  g->s2h = s2 && g->s2h_off ? reinterpret_cast<int*>(s2 + g->s2h_off) : nullptr;
+  g->mkeys = p.mkeys;
+  g->mcnt = p.mcnt;
+}
+
+size_t mfma_merge_tiles(const SearchArgs& p) { return mfma_merge_tiles(shape_of(p)); }
+
+bool plan_mfma_ssd(const SearchArgs& p, MfmaGeom* g) {
+  if (!plan_mfma_ssd(shape_of(p), kernel_path(), cu_count(), tuning(), g)) return false;
+  bind(p, g);
+  return true;
 }
 
 // Scratch bytes the MFMA path needs for this search (0: path not applicable).
 size_t mfma_ssd_scratch(const SearchArgs& p) {
   MfmaGeom g;
   return plan_mfma_ssd(p, &g) ? g.scratch_bytes : 0;
-}
-
-// Full-height block rows [row0, row0 + nrows) and full-width columns of a B = 16
-// SSD search; the caller routes partial rows / columns to the VALU kernels.
-static bool plan_mfma_ssd8(const SearchArgs& p, MfmaGeom* g);
-
-// Block-major (me_mfma_bm16_kernel) or 4x4-block tiles (me_mfma_ssd16_kernel)?
-// Block-major measured faster at every S (1080p, S = 2..103: tools/dbg/bm_sweep*.sh);
-// the tile kernel remains for row pitches / cur pointers that are not 16-byte aligned.
-static bool bm_auto(const SearchArgs& p) { return p.range <= 192; }
-
-// The automatic path's choice for `jobs` frames of p's shape per launch:
-// the band-walk kernel (lean: no prepass planes, ~1.0-1.3x the algorithmic
-// HBM bytes against ~7x) when its plan runs in one round of workgroups or
-// without splitting block rows into segments (each segment re-forms
-// 2 ceil(S/16) bands around it).  A single 1080p frame is 8 segments of 9
-// rows in one round: 37.5 against 37.8-38.8 us per call on the prepass pair;
-// 4K +-64 (2 segments of 68 rows): 265.9 against 254 us, the price of ~18
-// against ~122 MB of HBM traffic per search (profiles/r06h_ssd_ab.jsonl, one
-// box).  The round-5 figure of 68.8 us was the partial bottom row's second
-// launch, now searched inside the walk.
-// ME_PATH_MFMA_LEAN (force) takes the band-walk kernel whenever it applies.
-// g holds the block-major plan on entry and the band-walk plan on success.
-static bool use_bw(const SearchArgs& p, MfmaGeom* g, int jobs, bool force = false) {
-  if (!g->bm) return false;
-  MfmaGeom t = *g;
-  t.bmv = 0;
-  if (!plan_bw(p, &t, jobs) || (!force && t.bw_segs != 1 && !bw_one_round(t, jobs))) return false;
-  *g = t;
-  g->bmv_r = 1;
-  g->scratch_bytes = 0;
-  g->rp = nullptr;
-  g->s2 = g->s2h = nullptr;
-  return true;
-}
-
-bool plan_mfma_ssd(const SearchArgs& p, MfmaGeom* g) {
-  if (p.cost_kind != COST_SSD) return false;
-  if (p.blk == 8) return plan_mfma_ssd8(p, g);
-  if (p.blk != 16) return false;
-  if (mfma_disabled()) return false;
-  const int S = p.range, W = p.width, H = p.height;
-  if (S < 1 || W < 16 || H < 16) return false;
-  if (p.stride % 4 || (uintptr_t)p.cur % 4 || (uintptr_t)p.ref % 4) return false;
-  // block-major kernel for S <= 192 (ME_MFMA_BM=0|1: tuning build override)
-  const int force_bm = tuning().mfma_bm;
-  g->bm = S <= 192 && kernel_path() != 2 && (force_bm == 1 || (force_bm == 2 && bm_auto(p)));
-  // window row pitch: a workgroup's 8 blocks span 16 (tc1 - tc0) + 32 <= 16 (S / 8 + 8) + 32
-  // bytes (<= 544 up to S = 192)
-  g->bm_lp = S <= 64 ? 288 : 544;
-  if (g->bm && (p.stride % 16 || (uintptr_t)p.cur % 16)) g->bm = 0;  // 16-byte cur row loads
-  const int nxmax = min(48 + 2 * S + 1, W - 15);
-  const int ngx = (nxmax + 63) / 64;
-  if (ngx > 4 && !g->bm) return false;  // S > 103: the VALU kernels take it
-  const int nby = (H + 15) / 16;
-  const int r0 = p.block_row_begin, r1 = p.block_row_end;
-  g->row0 = r0;
-  g->nrows = r1 - r0;
-  if (g->nrows <= 0) return false;
-  // partial bottom block row (height hb): its lanes read the hb-row S2 plane
-  g->hb = H - 16 * (nby - 1);
-  g->hb_row = (g->hb < 16 && r1 == nby) ? nby - 1 : -1;
-  if (g->hb_row < 0) g->hb = 16;
-  g->nbx = W / 16;
-  g->tiles_x = (g->nbx + 3) / 4;
-  g->tiles_y = (g->nrows + 3) / 4;
-  g->ngx = ngx;
-  // chunk rows L = P0 + 16 KM: fewest (chunks x (L + P0)) steps on an interior tile
-  const int ny = min(48 + 2 * S + 1, H - 15);
-  int best = 1 << 30;
-  const int force_km = tuning().mfma_km;  // ME_MFMA_KM=2|3: tuning build override
-  for (int km = 2; km <= 3; km++) {  // km = 1 spills (its lone main-loop pass gets peeled)
-    if (force_km && km != force_km) continue;
-    const int L = 12 + MFMA_DLY + 16 * km, ch = (ny + L - 1) / L;
-    const int cost = ch * (L + 12 + MFMA_DLY);
-    if (cost < best) { best = cost; g->km = km; }
-  }
-  const int L = 12 + MFMA_DLY + 16 * g->km;
-  // groups per workgroup: two when the tile needs an even number of groups
-  // (whole tiles at 1080p +-32: no merge), else one (4K +-64: 3 workgroups)
-  g->ngxw = ngx % 2 == 0 ? 2 : 1;
-  if (tuning().mfma_ngxw) g->ngxw = tuning().mfma_ngxw;  // ME_MFMA_NGXW: tuning build
-  if (!g->bm && (ngx + g->ngxw - 1) / g->ngxw > 1 &&
-      (!p.mkeys || !p.mcnt || p.merge_tiles < mfma_merge_tiles(p)))
-    return false;  // tiles span workgroups: needs the merge buffers
-  g->lds = 4 * (L + 15) * (64 * g->ngxw + 32) + 16 * 8 + 16 * 4 + L * 256 * g->ngxw;
-  g->bm_wpr = (g->nbx + 7) / 8;
-  if (g->bm) g->lds = BM_HDR + 2 * 31 * g->bm_lp;
-  // ME_PATH_MFMA_LEAN, S <= 64 (window pitch 288): S2 formed in the workgroup,
-  // no prepass planes (ME_MFMA_S2K=0|1 overrides; tuning build)
-  const int s2k = tuning().mfma_s2k >= 0 ? tuning().mfma_s2k : kernel_path() == 3;
-  g->bmv = g->bm && g->bm_lp == BMV_LP && s2k;
-  // block rows per workgroup (ME_MFMA_S2R=1|2 overrides; tuning build).  Two
-  // rows share each band's S2 (6 bands for two rows at S = 32 instead of
-  // 5 + 5; 10 instead of 9 + 9 at S = 64) but synchronise 8 waves per barrier
-  // and leave a row idle in the other row's end bands: 16-frame batches, 1080p
-  // +-32 35.9 us per frame against 33.8 with one row, 4K +-64 289 against 323
-  // (profiles/r04f_ssd_ab.jsonl).  Two rows from S = 48 on.
-  g->bmv_r = tuning().mfma_s2r > 0 ? tuning().mfma_s2r : (S >= 48 ? 2 : 1);
-  if (g->bmv) g->lds = g->bmv_r == 2 ? bmv_lds<2>() : bmv_lds<1>();
-  g->mkeys = p.mkeys;
-  g->mcnt = p.mcnt;
-  g->ya0 = max(r0 * 16 - S, 0);
-  const int ya1 = min(r1 * 16 + S, H);
-  g->rp_rows = ya1 - g->ya0;
-  g->pitch = (W + 15) & ~15;
-  // + 80 rows of slack: the last chunk of a tile reads (masked) window rows and
-  // S2 entries up to L + 15 rows past the planes' last row.
-  // (the block-major kernel reads at most 15 rows past them, and its buffer
-  // loads are range-checked: 16 rows of slack)
-  g->rows_alloc = g->rp_rows + (g->bm ? 16 : 80);
-  // the last tile row's candidate rows start here (its lanes of the partial
-  // block row read s2h from there on)
-  const int tly_last = 16 * (r0 + 4 * (g->tiles_y - 1));
-  g->s2h_row0 = max(tly_last - S, 0) - g->ya0;
-  const size_t plane = (size_t)g->rows_alloc * g->pitch;
-  const size_t rp_alloc = (plane + 255) & ~(size_t)255;
-  const size_t s2_plane = plane * 4;
-  const size_t n_s2 = g->hb < 16 ? 2 : 1;
-  if (rp_alloc + n_s2 * s2_plane >= (1ull << 31)) return false;
-  g->rp_bytes = (uint32_t)plane;
-  g->s2_bytes = (uint32_t)(n_s2 * s2_plane);
-  g->s2h_off = (uint32_t)s2_plane;
-  g->scratch_bytes = rp_alloc + n_s2 * s2_plane;
-  g->rp = reinterpret_cast<int8_t*>(p.scratch);
-  g->s2 = p.scratch ? reinterpret_cast<int*>(p.scratch + rp_alloc) : nullptr;
-  g->s2h = p.scratch ? reinterpret_cast<int*>(p.scratch + rp_alloc + s2_plane) : nullptr;
-  // Automatic path, S <= 64: the band-walk kernel (me_band.hip) for the
-  // full-height rows, me_mfma_bmv_kernel for a partial bottom row, neither
-  // with scratch, when the frame's strips fill the CUs by themselves
-  // (use_bw); ME_PATH_MFMA_PREPASS keeps the prepass + block-major pair.
-  g->bw = 0;
-  if (kernel_path() == 0 || kernel_path() == 3) use_bw(p, g, 1, kernel_path() == 3);
-  if (g->bmv) {  // no planes: the kernel reads the reference plane
-    g->scratch_bytes = 0;
-    g->rp = nullptr;
-    g->s2 = g->s2h = nullptr;
-  }
-  return true;
-}
-
-// 8x8 blocks: full-height block rows only (a partial bottom row goes to the
-// VALU kernels), one workgroup per 4x4-block tile walking its 64-column groups,
-// chunks of 16 ME_SSD8_KM rows.
-static bool plan_mfma_ssd8(const SearchArgs& p, MfmaGeom* g) {
-  if (mfma_disabled()) return false;
-  const int S = p.range, W = p.width, H = p.height;
-  if (S < 1 || W < 8 || H < 8) return false;
-  if (p.stride % 4 || (uintptr_t)p.cur % 4 || (uintptr_t)p.ref % 4) return false;
-  const int nby = (H + 7) / 8;
-  const int r0 = p.block_row_begin;
-  int r1 = p.block_row_end;
-  if (r1 == nby && H % 8) r1--;
-  g->row0 = r0;
-  g->nrows = r1 - r0;
-  if (g->nrows <= 0) return false;
-  g->hb = 8;
-  g->hb_row = -1;
-  g->bm = 0;
-  g->bmv = 0;
-  g->bmv_r = 1;
-  g->bw = 0;
-  g->nbx = W / 8;
-  g->tiles_x = (g->nbx + 3) / 4;
-  g->tiles_y = (g->nrows + 3) / 4;
-  const int nxmax = min(24 + 2 * S + 1, W - 7);
-  g->ngx = (nxmax + 63) / 64;
-  g->ngxw = g->ngx;  // one workgroup walks all of a tile's groups
-  g->km = ME_SSD8_KM;  // L = 16 km candidate rows per chunk
-  const int L = 16 * g->km;
-  // 4 copies + keys + S2 table + the words after each copy granule: 31.9 KB (two tiles), 5 workgroups per CU
-  g->lds = 4 * (L + 8) * ME_SSD8_WP + 16 * ME_SSD8_NT * 12 + (L + 1) * 256 + (L + 8) * (ME_SSD8_WP / 16) * 4;
-  g->ya0 = max(r0 * 8 - S, 0);
-  const int ya1 = min(r1 * 8 + S, H);
-  g->rp_rows = ya1 - g->ya0;
-  g->pitch = (W + 15) & ~15;
-  g->rows_alloc = g->rp_rows + 80;
-  g->s2h_row0 = 0;
-  // S2 plane only: the kernel stages the reference rows itself (no r ^ 0x80 plane)
-  const size_t plane = (size_t)g->rows_alloc * g->pitch;
-  const size_t s2_plane = plane * 4;
-  if (s2_plane >= (1ull << 31)) return false;
-  g->rp_bytes = 0;
-  g->s2_bytes = (uint32_t)s2_plane;
-  g->s2h_off = 0;
-  g->scratch_bytes = s2_plane;
-  g->rp = nullptr;
-  g->s2 = p.scratch ? reinterpret_cast<int*>(p.scratch) : nullptr;
-  g->s2h = nullptr;
-  g->mkeys = p.mkeys;
-  g->mcnt = p.mcnt;
-  return true;
-}
-
-// Main-kernel workgroups per job: a block row each, or R rows each on the
-// lean path (me_mfma_bmv_kernel<R>).
-static int wgs_per_job(const MfmaGeom& g) {
-  return g.bmv ? (g.nrows + g.bmv_r - 1) / g.bmv_r * g.bm_wpr : g.nrows * g.bm_wpr;
 }
 
 // The one-job table of a single search (its own pointers, its own scratch).
@@ -2117,42 +1920,18 @@ hipError_t launch_mfma_ssd(const SearchArgs& p, const MfmaGeom& g, hipStream_t s
 }
 
 // ------------------------------------------------------------------ batches
-// A batch of frames with one geometry shares one prepass launch and one
-// block-major launch: a 1080p search is one round of workgroups per CU, so a
-// launch per frame pays the grid's fill and drain every frame.
-static constexpr size_t MFMA_BATCH_SCRATCH = (size_t)1 << 30;  // prepass planes per launch
-
-static size_t batch_stride(const MfmaGeom& g) { return (g.scratch_bytes + 255) & ~(size_t)255; }
-
-// Jobs per batched launch for this geometry: 0 when the batch path does not
-// apply (not the block-major kernel, or one job's planes alone exceed the cap).
-static int batch_jobs(const MfmaGeom& g, int n) {
-  if (!g.bm || n < 2) return 0;
-  if (g.bmv || g.bw) return n < MAX_JOBS ? n : MAX_JOBS;  // no prepass planes
-  const size_t per = MFMA_BATCH_SCRATCH / batch_stride(g);
-  const int m = (int)(per < (size_t)MAX_JOBS ? per : (size_t)MAX_JOBS);
-  return m >= 2 ? (n < m ? n : m) : 0;
-}
-
+// plan_mfma_batch (me_mfma_plan.cpp) decides how n equal jobs run: the
+// context sizes its scratch with it, the launcher launches what it planned.
 size_t mfma_batch_scratch(const SearchArgs& p, int n) {
-  MfmaGeom g;
-  if (!plan_mfma_ssd(p, &g) || g.bmv || g.bw) return 0;
-  // launch_mfma_jobs runs the batch job by job, each on its own single-frame
-  // plan, when a job has a partial right column or its planes are not
-  // aligned like job 0's: the scratch then has to hold one job's prepass
-  // planes (a batch that fell back with none ran on the VALU kernels)
-  const size_t one = g.scratch_bytes;
-  if (g.nbx < p.nbx) return one;
-  if (n >= 2 && kernel_path() == 0 && tuning().mfma_batch != 0 && use_bw(p, &g, n < MAX_JOBS ? n : MAX_JOBS))
-    return one;  // the batch runs on the band-walk kernel (no planes) unless it falls back
-  const int m = batch_jobs(g, n);
-  return m ? ((size_t)m * batch_stride(g) > one ? (size_t)m * batch_stride(g) : one) : one;
+  MfmaBatch b;
+  plan_mfma_batch(shape_of(p), n, MFMA_SCRATCH_UNLIMITED, kernel_path(), cu_count(), tuning(), &b);
+  return b.need;
 }
 
 bool launch_mfma_jobs(const SearchArgs& base, const SearchJob* jobs, int n, hipStream_t stream,
                       hipError_t* err) {
   *err = hipSuccess;
-  if (base.cost_kind != COST_SSD || n < 2 || tuning().mfma_batch == 0) return false;
+  if (n < 2) return false;
   for (int i = 1; i < n; i++)  // one geometry: the same rows of same-sized frames
     if (jobs[i].r0 != jobs[0].r0 || jobs[i].r1 != jobs[0].r1 ||
         jobs[i].ref_row0 != jobs[0].ref_row0 || jobs[i].cur_row0 != jobs[0].cur_row0)
@@ -2166,28 +1945,24 @@ bool launch_mfma_jobs(const SearchArgs& base, const SearchJob* jobs, int n, hipS
   p.block_row_end = jobs[0].r1;
   p.mv = jobs[0].mv;
   p.cost = jobs[0].cost;
-  MfmaGeom g;
-  if (jobs[0].r1 <= jobs[0].r0 || !plan_mfma_ssd(p, &g)) return false;
-  // plan_mfma_ssd saw job 0's pointers only: every job's planes must meet the
-  // same alignment (4-byte DMA sources; the block-major kernel's 16-byte cur
-  // row loads), else the batch runs job by job, each planned on its own
+  MfmaBatch b;
+  if (!plan_mfma_batch(shape_of(p), n, p.scratch ? p.scratch_bytes : 0, kernel_path(), cu_count(),
+                       tuning(), &b) || b.jobs < 2)
+    return false;
+  const MfmaGeom& g = b.g;
+  // the plan saw job 0's pointers only: every job's planes must meet the same
+  // alignment (4-byte DMA sources; the block-major kernel's 16-byte cur row
+  // loads), else the batch runs job by job, each planned on its own
+  const int need = ALIGN_4 | (g.bm ? ALIGN_CUR16 : 0);
   for (int i = 1; i < n; i++)
-    if ((uintptr_t)jobs[i].ref % 4 || (uintptr_t)jobs[i].cur % (g.bm ? 16 : 4)) return false;
-  // a launch of several frames may fill the CUs where one frame does not
-  if (!g.bw && kernel_path() == 0) use_bw(p, &g, n < MAX_JOBS ? n : MAX_JOBS);
-  const bool lean = g.bmv || g.bw;  // no prepass planes
-  const size_t stride = lean ? 0 : batch_stride(g);
-  int m = batch_jobs(g, n);
-  if (!lean && (!base.scratch || (m && (size_t)m * stride > base.scratch_bytes)))
-    m = base.scratch ? (int)(base.scratch_bytes / stride) : 0;
-  if (g.bw) plan_bw(p, &g, m);  // segments sized for m jobs per launch
-  if (m < 2 || g.nbx < p.nbx) return false;  // (a partial right column: job by job)
+    if ((align_class(p.stride, jobs[i].ref, jobs[i].cur) & need) != need) return false;
+  bind(p, &b.g);
   note_path(mfma_path(p, g));
-  for (int i0 = 0; i0 < n && *err == hipSuccess; i0 += m) {
+  for (int i0 = 0; i0 < n && *err == hipSuccess; i0 += b.jobs) {
     MfmaJobs jb;
-    jb.n = n - i0 < m ? n - i0 : m;
+    jb.n = n - i0 < b.jobs ? n - i0 : b.jobs;
     jb.wgs = wgs_per_job(g);
-    jb.scratch_stride = stride;
+    jb.scratch_stride = b.stride;
     for (int j = 0; j < jb.n; j++) {
       const SearchJob& J = jobs[i0 + j];
       jb.ref[j] = J.ref;

@@ -12,7 +12,11 @@
 //     src/common/utils.c:61-67);
 //   - the VALU launch planners (me_valu_plan.cpp: plan_fast, plan_flow) over
 //     seeded random shapes, alignment classes, CU counts and tuning overrides,
-//     checking what the kernels rely on in every accepted plan.
+//     checking what the kernels rely on in every accepted plan;
+//   - the matrix-core SSD planners (me_mfma_plan.cpp: the single-search plan,
+//     plan_bw, the batch plan) likewise, over every kernel path: the batch's
+//     planes fit the scratch that was sized for it, LDS and plane bounds, the
+//     kernel instances the launchers dispatch, the band walk's cover.
 // Exit status 0 and "san ok" on success; the sanitizers abort otherwise.
 #include <stdint.h>
 #include <stdio.h>
@@ -25,6 +29,7 @@
 
 #include "me.h"
 #include "me_geom.h"
+#include "me_mfma_geom.h"
 #include "me_oracle.h"
 #include "me_tuning.h"
 
@@ -267,11 +272,157 @@ static void valu_planners() {
   }
 }
 
+// What launch_bw and the band-walk kernel rely on in a plan for `jobs` jobs
+// per launch (g.nrows counts a partial bottom row, the walk's rows do not).
+static void check_bw(const me::MfmaGeom& g, int jobs) {
+  const int rows = g.nrows - (g.hb_row >= 0 ? 1 : 0);
+  CHECK(g.bw == 1 && rows >= 1);
+  CHECK(g.bw_strips * g.bw_cols >= g.nbx && (g.bw_strips - 1) * g.bw_cols < g.nbx);
+  CHECK(g.bw_segs >= 1 && g.bw_seg_rows >= 1);
+  CHECK((long)g.bw_segs * g.bw_seg_rows >= rows);
+  CHECK((long)(g.bw_segs - 1) * g.bw_seg_rows < rows);  // no segment is empty
+  CHECK(g.bw_wpc * g.bw_cols == g.bw_nsw);
+  const int inst[6][2] = {{6, 160}, {4, 160}, {3, 160}, {3, 224}, {2, 160}, {2, 224}};  // launch_bw's
+  bool found = false;
+  for (auto& i : inst) found |= g.bw_cols == i[0] && g.bw_lp == i[1];
+  CHECK(found && g.bw_ns == 2 && g.bw_nsw == 12 && g.bw_pw == 4);
+  CHECK(g.lds <= 160 * 1024);
+  CHECK(g.lds == me::bw_lds_bytes(g.bw_lp, g.bw_pp, g.bw_ns, g.bw_nsw) +
+                     me::bw_lds_hb_bytes(g.bw_pp, g.bw_ns, g.bw_hb));
+  CHECK(g.bw_hb == 0 || g.hb_row >= 0);
+  if (!g.bw_xt) return;
+  // per-XCD tail split: the launch's grid, decoded as bw_item decodes it,
+  // covers every row of every strip item once
+  CHECK(g.bw_segs == 1 && g.bw_seg_rows == rows && g.bw_cx >= 1);
+  const int U = jobs * g.bw_strips, q = U >> 3, rem = U & 7;
+  const long grid = me::bw_xt_grid(U, g.bw_cx, rows);
+  CHECK(grid % 8 == 0 && grid < (1L << 31));
+  std::vector<int> covered(U, 0);
+  for (long b = 0; b < grid; b++) {
+    const int x = (int)(b & 7), m = (int)(b >> 3);
+    const int nx = q + (x < rem ? 1 : 0), u0 = x * q + (x < rem ? x : rem);
+    int mainx, kx, st, L;
+    me::bw_xcd_split(nx, g.bw_cx, rows, &mainx, &kx, &st, &L);
+    if (m < mainx) {
+      covered[u0 + m] += rows;
+      continue;
+    }
+    const int t = m - mainx;
+    if (t >= kx * st) continue;
+    const int seg = t / kx, r0 = seg * L;
+    CHECK(r0 < rows);
+    covered[u0 + mainx + t % kx] += (r0 + L < rows ? r0 + L : rows) - r0;
+  }
+  for (int u = 0; u < U; u++) CHECK(covered[u] == rows);
+}
+
+// The matrix-core SSD planners (me_mfma_plan.cpp) over random shapes, paths,
+// CU counts, job counts and the tuning overrides that keep a plan valid.
+static void mfma_planners() {
+  const int cu_counts[] = {64, 256, 304};
+  int accepted = 0, walks = 0, batches = 0;
+  for (int t = 0; t < 6000; t++) {
+    me::MfmaShape s;
+    s.width = 1 + (int)(next_u64() % (t % 16 ? 4200 : 17000));
+    s.height = 1 + (int)(next_u64() % (t % 16 ? 2400 : 17000));
+    if (next_u64() % 4) s.width = (s.width + 15) & ~15;  // (else a partial right column)
+    s.stride = s.width + (next_u64() % 3 ? 0 : 4 * (int)(next_u64() % 16));
+    if (next_u64() % 2) s.stride = (s.stride + 15) & ~15;
+    s.blk = next_u64() % 8 ? (next_u64() % 4 ? 16 : 8) : (int)(next_u64() % 33);
+    s.range = next_u64() % 3 ? 1 + (int)(next_u64() % 64) : (int)(next_u64() % 260);
+    s.cost = next_u64() % 16 ? me::COST_SSD : me::COST_SAD;
+    const int blk = s.blk > 0 ? s.blk : 1, nby = (s.height + blk - 1) / blk;
+    s.row_begin = next_u64() % 2 ? 0 : (int)(next_u64() % (nby + 1));
+    s.row_end = next_u64() % 2 ? nby : s.row_begin + (int)(next_u64() % (nby - s.row_begin + 1));
+    s.nbx = (s.width + blk - 1) / blk;
+    const uintptr_t mods[] = {0, 0, 0, 0, 0, 0, 0, 4, 8, 2};
+    s.align = me::align_class(s.stride, (const void*)(0x10000 + mods[next_u64() % 10]),
+                              (const void*)(0x20000 + mods[next_u64() % 10]));
+    s.merge_tiles = next_u64() % 4 ? me::mfma_merge_tiles(s) : (next_u64() % 2 ? 0 : 7);
+    const int path = (int)(next_u64() % 5), cus = cu_counts[next_u64() % 3];
+    me::Tuning tu;
+    if (t % 4 == 3) {
+      tu.mfma_s2k = (int)(next_u64() % 3) - 1;
+      tu.mfma_s2r = (int)(next_u64() % 3);
+      tu.mfma_batch = next_u64() % 4 ? -1 : 0;
+      tu.bw = next_u64() % 4 ? -1 : 0;
+      tu.bw_hb = next_u64() % 2 ? -1 : 0;
+      tu.bw_xt = next_u64() % 2 ? -1 : 0;
+      tu.bw_seg = next_u64() % 2 ? 0 : 1 + (int)(next_u64() % 40);
+    }
+    me::MfmaGeom g;
+    if (!me::plan_mfma_ssd(s, path, cus, tu, &g)) {
+      me::MfmaBatch b;
+      CHECK(!me::plan_mfma_batch(s, 8, me::MFMA_SCRATCH_UNLIMITED, path, cus, tu, &b));
+      CHECK(b.jobs == 0 && b.need == 0);
+      continue;
+    }
+    accepted++;
+    CHECK(path != 1 && s.cost == me::COST_SSD && (s.blk == 8 || s.blk == 16) && s.range >= 1);
+    CHECK(s.align & me::ALIGN_4);
+    CHECK(!g.rp && !g.s2 && !g.s2h && !g.mkeys && !g.mcnt);  // the launchers bind them
+    CHECK(g.row0 == s.row_begin && g.nrows >= 1 && g.row0 + g.nrows <= s.row_end);
+    CHECK(g.nbx == s.width / s.blk && g.nbx >= 1);
+    // (b) LDS: what a CU has, and 64 KB unless the launcher raises the limit
+    // (the 8x8 kernel, the tile kernel and the band walk call lds_attr)
+    CHECK(g.lds > 0 && g.lds <= 160 * 1024);
+    if (g.bm && !g.bw) CHECK(g.lds <= 64 * 1024);
+    // (c) the planes: the arithmetic the prepass and the kernels index by
+    CHECK(g.ya0 >= 0 && g.rp_rows >= 1 && g.ya0 + g.rp_rows <= s.height);
+    CHECK(g.rows_alloc >= g.rp_rows + 16 && g.pitch >= s.width && g.pitch % 16 == 0);
+    const uint64_t plane = (uint64_t)g.rows_alloc * g.pitch;
+    const uint64_t n_s2 = s.blk == 16 && g.hb < 16 ? 2 : 1;
+    CHECK(g.rp_bytes == (s.blk == 16 ? plane : 0) && g.s2_bytes == n_s2 * 4 * plane);
+    CHECK(g.s2h_off == (s.blk == 16 ? 4 * plane : 0));
+    const uint64_t all = (((uint64_t)g.rp_bytes + 255) & ~(uint64_t)255) + g.s2_bytes;
+    CHECK(all < (1ull << 31));
+    CHECK(g.scratch_bytes == (g.bw || g.bmv ? 0 : all));
+    CHECK(g.hb_row < 0 || (g.hb < 16 && g.hb_row == s.row_end - 1 && g.s2h_row0 >= 0));
+    // (e) the tile kernel's instances
+    if (s.blk == 16 && !g.bm) {
+      CHECK((g.ngxw == 1 || g.ngxw == 2) && (g.km == 2 || g.km == 3) && g.ngx >= 1 && g.ngx <= 4);
+      CHECK((g.ngx + g.ngxw - 1) / g.ngxw == 1 || s.merge_tiles >= me::mfma_merge_tiles(s));
+    }
+    if (g.bmv) CHECK(g.bm && g.bm_lp == me::BMV_LP && (g.bmv_r == 1 || g.bmv_r == 2));
+    if (g.bm) CHECK(me::wgs_per_job(g) >= 1);  // (the block-major kernels' grid)
+    // (d) the band walk, as the single plan and re-planned for more jobs
+    if (g.bw) check_bw(g, 1);
+    const int jobs = 1 + (int)(next_u64() % 40);
+    if (s.blk == 16) {
+      me::MfmaGeom w = g;
+      if (me::plan_bw(s, cus, tu, &w, jobs)) {
+        walks++;
+        check_bw(w, jobs);
+        CHECK(me::bw_one_round(w, jobs, cus) == ((long)jobs * w.bw_strips * w.bw_segs <= cus));
+      }
+    }
+    // (a) the batch: what the context sizes is what the launcher gets
+    me::MfmaBatch need, got;
+    CHECK(me::plan_mfma_batch(s, jobs, me::MFMA_SCRATCH_UNLIMITED, path, cus, tu, &need));
+    CHECK(need.jobs == 0 || (need.jobs >= 2 && need.jobs <= jobs && need.jobs <= me::MAX_JOBS));
+    CHECK(need.need >= (size_t)need.jobs * need.stride && need.need >= g.scratch_bytes);
+    CHECK((need.stride == 0) == (need.jobs == 0 || need.g.bw || need.g.bmv));
+    if (need.jobs) {
+      batches++;
+      CHECK(need.g.bm && need.g.nbx == s.nbx && need.stride % 256 == 0);
+      CHECK(need.stride == 0 || need.stride >= need.g.scratch_bytes);
+      if (need.g.bw) check_bw(need.g, need.jobs);
+    }
+    CHECK(me::plan_mfma_batch(s, jobs, need.need, path, cus, tu, &got));
+    CHECK(got.jobs == need.jobs && got.stride == need.stride);  // sized once, launched as sized
+    const size_t avail = next_u64() % 2 ? 0 : (size_t)(next_u64() % (need.need + 1));
+    CHECK(me::plan_mfma_batch(s, jobs, avail, path, cus, tu, &got));
+    CHECK((size_t)got.jobs * got.stride <= avail && got.jobs <= need.jobs && got.jobs != 1);
+  }
+  CHECK(accepted > 2000 && walks > 800 && batches > 600);
+}
+
 int main() {
   pool();
   planner();
   files();
   valu_planners();
+  mfma_planners();
   printf("san ok\n");
   return 0;
 }
