@@ -194,36 +194,30 @@ me_status check_args(me_ctx* c, const void* ref, const void* cur, int width, int
   return ME_OK;
 }
 
-SearchArgs make_args(const uint8_t* ref, int ref_row0, const uint8_t* cur, int cur_row0,
-                         int width, int height, int stride, int blk, int range, int cost,
-                         int r0, int r1, int16_t* mv, uint32_t* cst) {
-  SearchArgs p;
-  p.ref = ref;
-  p.cur = cur;
-  p.ref_row0 = ref_row0;
-  p.cur_row0 = cur_row0;
+SearchArgs make_args(const SearchJob& J, int width, int height, int stride, int blk, int range,
+                     int cost) {
+  SearchArgs p{};  // (no context buffers yet: attach_scratch)
   p.width = width;
   p.height = height;
   p.stride = stride;
   p.blk = blk;
   p.range = range;
   p.nbx = (width + blk - 1) / blk;
-  p.block_row_begin = r0;
-  p.block_row_end = r1;
   p.cost_kind = cost;
-  p.mv = mv;
-  p.cost = cst;
-  // Bytes the kernels may read from each plane (the DMA descriptors' range):
-  // the rows the stripe contract guarantees resident (include/me.h).
-  p.ref_bytes = ref_resident_bytes(r1, blk, range, height, ref_row0, stride, width);
-  p.cur_bytes = cur_resident_bytes(r1, blk, height, cur_row0, stride, width);
-  p.sched = nullptr;
-  p.scratch = nullptr;
-  p.scratch_bytes = 0;
-  p.mkeys = nullptr;
-  p.mcnt = nullptr;
-  p.merge_tiles = 0;
-  return p;
+  return job_args(p, J);
+}
+
+me_status check_stripe(me_ctx* c, int nby, int blk, int range, int r0, int r1, int ref_row0,
+                       int cur_row0, int job) {
+  const int need_ref0 = r0 * blk - range > 0 ? r0 * blk - range : 0;
+  const bool rows = r0 < 0 || r1 > nby || r0 > r1;
+  const bool ref = ref_row0 < 0 || ref_row0 > need_ref0, cur = cur_row0 < 0 || cur_row0 > r0 * blk;
+  if (!rows && !ref && !cur) return ME_OK;
+  char pre[24] = "";
+  if (job >= 0) snprintf(pre, sizeof pre, "job %d: ", job);
+  if (rows) return fail(c, ME_EINVAL, "%sblock rows [%d, %d)", pre, r0, r1);
+  if (ref) return fail(c, ME_EINVAL, "%sref_row0 %d", pre, ref_row0);
+  return fail(c, ME_EINVAL, "%scur_row0 %d", pre, cur_row0);
 }
 
 me_status attach_scratch(me_ctx* c, Dev& d, SearchArgs& p, bool cap, int batch) {
@@ -286,30 +280,11 @@ me_status order_on(me_ctx* c, Dev& d, hipStream_t s) {
   return ME_OK;
 }
 
-me_status launch_ordered(me_ctx* c, Dev& d, SearchArgs& p, hipStream_t s) {
+me_status launch_ordered(me_ctx* c, Dev& d, const SearchArgs& base, const SearchJob* jobs, int n,
+                         hipStream_t s, bool cap) {
   ME_CTX_PATH_SCOPE(c, d);
   // Captured launches run only when their graph does (me_graph_launch orders
   // it): no ordering and no state change at capture time.
-  const bool cap = capturing(s);
-  if (!cap) {
-    me_status st = order_on(c, d, s);
-    if (st != ME_OK) return st;
-  }
-  const hipError_t e = launch_search(p, s, nullptr);
-  if (e != hipSuccess) {
-    if (!cap) {
-      (void)hipMemsetAsync(d.sched, 0, SCHED_WORDS * 4, s);
-      if (d.mkeys) (void)hipMemsetAsync(d.mkeys, 0xFF, d.merge_cap * 16 * 8, s);
-      if (d.mcnt) (void)hipMemsetAsync(d.mcnt, 0, d.merge_cap * 4, s);
-    }
-    return fail(c, ME_EDEVICE, "search launch: %s", hipGetErrorString(e));
-  }
-  return ME_OK;
-}
-
-me_status launch_jobs_ordered(me_ctx* c, Dev& d, const SearchArgs& base, const SearchJob* jobs,
-                              int n, hipStream_t s, bool cap) {
-  ME_CTX_PATH_SCOPE(c, d);
   if (!cap) {
     me_status st = order_on(c, d, s);
     if (st != ME_OK) return st;
@@ -505,10 +480,10 @@ me_status stripe_upload_launch(me_ctx* c, Dev& d, const uint8_t* ref, const uint
                              cur_rows, hipMemcpyHostToDevice, d.stream));
   int16_t* dmv = reinterpret_cast<int16_t*>(d.rec);
   uint32_t* dcost = reinterpret_cast<uint32_t*>(d.rec + max_blocks * 4);
-  me::SearchArgs p = make_args(d.ref, y_ref0, d.cur, y_cur0, width, height, width, blk, range,
-                               cost, r0, r1, dmv, dcost);
+  const me::SearchJob J{d.ref, y_ref0, d.cur, y_cur0, r0, r1, dmv, dcost};
+  me::SearchArgs p = make_args(J, width, height, width, blk, range, cost);
   if ((s = attach_scratch(c, d, p)) != ME_OK) return s;
-  return launch_ordered(c, d, p, d.stream);
+  return launch_ordered(c, d, p, &J, 1, d.stream);
 }
 
 // Multi-device frame search: row stripes balanced by me_plan_stripes' per-row
@@ -932,10 +907,10 @@ me_status me_full_search(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int 
   int16_t* dmv = reinterpret_cast<int16_t*>(d.rec);
   uint32_t* dcost = reinterpret_cast<uint32_t*>(d.rec + nb * 4);
   const int nby = (height + blk - 1) / blk;
-  me::SearchArgs p = make_args(d.ref, 0, d.cur, 0, width, height, width, blk, range, cost, 0,
-                               nby, dmv, dcost);
+  const me::SearchJob J{d.ref, 0, d.cur, 0, 0, nby, dmv, dcost};
+  me::SearchArgs p = make_args(J, width, height, width, blk, range, cost);
   if ((s = attach_scratch(c, d, p)) != ME_OK) return s;
-  if ((s = launch_ordered(c, d, p, d.stream)) != ME_OK) return s;
+  if ((s = launch_ordered(c, d, p, &J, 1, d.stream)) != ME_OK) return s;
   HIPCHK(c, hipMemcpyAsync(mv_xy, dmv, nb * 4, hipMemcpyDeviceToHost, d.stream));
   if (block_cost)
     HIPCHK(c, hipMemcpyAsync(block_cost, dcost, nb * 4, hipMemcpyDeviceToHost, d.stream));
@@ -950,16 +925,13 @@ me_status me_full_search_stripe_device(me_ctx* c, const uint8_t* d_ref, int ref_
   me_status s = check_args(c, d_ref, d_cur, width, height, stride, blk, range, cost, d_mv);
   if (s != ME_OK) return s;
   const int nby = (height + blk - 1) / blk;
-  if (r0 < 0 || r1 > nby || r0 > r1) return fail(c, ME_EINVAL, "block rows [%d, %d)", r0, r1);
-  const int need_ref0 = r0 * blk - range > 0 ? r0 * blk - range : 0;
-  if (ref_row0 < 0 || ref_row0 > need_ref0) return fail(c, ME_EINVAL, "ref_row0 %d", ref_row0);
-  if (cur_row0 < 0 || cur_row0 > r0 * blk) return fail(c, ME_EINVAL, "cur_row0 %d", cur_row0);
+  if ((s = me::check_stripe(c, nby, blk, range, r0, r1, ref_row0, cur_row0, -1)) != ME_OK) return s;
   c->err[0] = 0;
-  me::SearchArgs p = make_args(d_ref, ref_row0, d_cur, cur_row0, width, height, stride, blk,
-                               range, cost, r0, r1, d_mv, d_cost);
+  const me::SearchJob J{d_ref, ref_row0, d_cur, cur_row0, r0, r1, d_mv, d_cost};
+  me::SearchArgs p = make_args(J, width, height, stride, blk, range, cost);
   const bool cap = me::capturing((hipStream_t)stream);
   if ((s = attach_scratch(c, c->devs[0], p, cap)) != ME_OK) return s;
-  if ((s = launch_ordered(c, c->devs[0], p, (hipStream_t)stream)) != ME_OK) return s;
+  if ((s = launch_ordered(c, c->devs[0], p, &J, 1, (hipStream_t)stream, cap)) != ME_OK) return s;
   c->devs[0].async_unchecked = true;
   return ME_OK;
 }
@@ -981,23 +953,14 @@ me_status me_search_stripes_device(me_ctx* c, int width, int height, int stride,
                              J.d_mv_xy);
     if (s != ME_OK) return s;
     const int r0 = J.block_row_begin, r1 = J.block_row_end;
-    if (r0 < 0 || r1 > nby || r0 > r1)
-      return fail(c, ME_EINVAL, "job %d: block rows [%d, %d)", i, r0, r1);
-    const int need_ref0 = r0 * blk - range > 0 ? r0 * blk - range : 0;
-    if (J.ref_row0 < 0 || J.ref_row0 > need_ref0)
-      return fail(c, ME_EINVAL, "job %d: ref_row0 %d", i, J.ref_row0);
-    if (J.cur_row0 < 0 || J.cur_row0 > r0 * blk)
-      return fail(c, ME_EINVAL, "job %d: cur_row0 %d", i, J.cur_row0);
+    if ((s = me::check_stripe(c, nby, blk, range, r0, r1, J.ref_row0, J.cur_row0, i)) != ME_OK) return s;
     js[i] = me::SearchJob{J.d_ref, J.ref_row0, J.d_cur, J.cur_row0, r0, r1, J.d_mv_xy, J.d_block_cost};
     // grow the device scratch to the largest job (the MFMA SSD path runs job by job)
-    me::SearchArgs p = make_args(J.d_ref, J.ref_row0, J.d_cur, J.cur_row0, width, height, stride,
-                                 blk, range, cost, r0, r1, J.d_mv_xy, J.d_block_cost);
+    me::SearchArgs p = make_args(js[i], width, height, stride, blk, range, cost);
     if ((s = attach_scratch(c, d, p, cap)) != ME_OK) return s;
   }
   // geometry, cost and the (final) scratch buffers every job's launch takes
-  base = make_args(jobs[0].d_ref, jobs[0].ref_row0, jobs[0].d_cur, jobs[0].cur_row0, width, height,
-                   stride, blk, range, cost, jobs[0].block_row_begin, jobs[0].block_row_end,
-                   jobs[0].d_mv_xy, jobs[0].d_block_cost);
+  base = make_args(js[0], width, height, stride, blk, range, cost);
   {
     // jobs of one geometry (a batch of whole frames) share the SSD launches
     bool same = true;
@@ -1009,7 +972,7 @@ me_status me_search_stripes_device(me_ctx* c, int width, int height, int stride,
     if (s != ME_OK) return s;
   }
   c->err[0] = 0;
-  me_status s = me::launch_jobs_ordered(c, d, base, js.data(), n_jobs, (hipStream_t)stream, cap);
+  me_status s = launch_ordered(c, d, base, js.data(), n_jobs, (hipStream_t)stream, cap);
   if (s == ME_OK) d.async_unchecked = true;
   return s;
 }
@@ -1024,10 +987,11 @@ me_status me_full_search_batch_device(me_ctx* c, const uint8_t* d_ref, size_t re
   me_status s = check_args(c, d_ref, d_cur, width, height, stride, blk, range, cost, d_mv);
   if (s != ME_OK) return s;
   const int nby = (height + blk - 1) / blk;
-  if (r0 < 0 || r1 > nby || r0 > r1) return fail(c, ME_EINVAL, "block rows [%d, %d)", r0, r1);
+  // (the rows only: the frames' ref_row0 / cur_row0 are reported per job below)
+  if ((s = me::check_stripe(c, nby, blk, range, r0, r1, 0, 0, -1)) != ME_OK) return s;
   // every frame's resident rows inside its stride (frames must not overlap)
-  const me::SearchArgs p = make_args(d_ref, ref_row0, d_cur, cur_row0, width, height, stride, blk,
-                                     range, cost, r0, r1, d_mv, d_cost);
+  const me::SearchArgs p = make_args(me::SearchJob{d_ref, ref_row0, d_cur, cur_row0, r0, r1, d_mv, d_cost},
+                                     width, height, stride, blk, range, cost);
   if (n_frames > 1 && (ref_frame_stride < p.ref_bytes || cur_frame_stride < p.cur_bytes))
     return fail(c, ME_EINVAL, "frame strides %zu / %zu below a frame's %u / %u bytes",
                 ref_frame_stride, cur_frame_stride, p.ref_bytes, p.cur_bytes);

@@ -125,6 +125,24 @@ struct SearchJob {
   uint32_t* cost;
 };
 
+// The single-job arguments of job J (geometry, cost and context buffers from
+// base): the one place the resident bytes of a job are derived.
+inline SearchArgs job_args(const SearchArgs& base, const SearchJob& J) {
+  SearchArgs q = base;
+  q.ref = J.ref;
+  q.ref_row0 = J.ref_row0;
+  q.cur = J.cur;
+  q.cur_row0 = J.cur_row0;
+  q.block_row_begin = J.r0;
+  q.block_row_end = J.r1;
+  q.mv = J.mv;
+  q.cost = J.cost;
+  q.ref_bytes = ref_resident_bytes(J.r1, base.blk, base.range, base.height, J.ref_row0, base.stride,
+                                   base.width);
+  q.cur_bytes = cur_resident_bytes(J.r1, base.blk, base.height, J.cur_row0, base.stride, base.width);
+  return q;
+}
+
 // The flow kernel's job table (kernel argument): job j owns launch tiles
 // [tile_pre[j], tile_pre[j + 1]).  A batch of frames or stripes (the per-rank
 // step of a multi-GPU split) fills the GPU in one launch.
@@ -152,9 +170,9 @@ inline int align_class(int stride, const void* ref, const void* cur) {
          (stride % 16 == 0 && r % 16 == 0 ? ALIGN_REF16 : 0) | (c % 16 == 0 ? ALIGN_CUR16 : 0);
 }
 
-// What a plan depends on (and the plan cache's key): the frame, the search,
-// the block rows planned for (every job's rows of a batched launch) and the
-// alignment class of the planes.
+// What a plan depends on (and, with the CU count and the Tuning, the plan
+// cache's key): the frame, the search, the block rows planned for (every job's rows of a
+// batched launch) and the alignment class of the planes.
 struct PlanShape {
   int width, height, stride, blk, range, cost, rows, align;
   bool operator==(const PlanShape& o) const {
@@ -171,5 +189,13 @@ struct Tuning;  // me_tuning.h
 bool plan_fast(const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g, int* k_out);
 // The flow kernel's plan (me_flow_kernel<16, 13>); false: the item kernel's turn.
 bool plan_flow(const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g);
+
+// Plans depend only on the shape: cached_plan keeps them (process-wide, one
+// ring of 8 per planner under a mutex: the per-device host threads share them)
+// so a steady stream of same-shape searches pays the planner once.  s.align is
+// the planes' whole class (align_class; of every job of a batch): each planner
+// is keyed by what it reads of it.  K may be null.
+enum PlanKind { PLAN_ITEM = 0, PLAN_FLOW = 1 };
+bool cached_plan(PlanKind kind, const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g, int* K);
 
 }  // namespace me

@@ -1,6 +1,7 @@
 // me_internal.h -- context internals shared by the C-ABI translation units
-// (me_api.hip: single-frame and stripe entry points; me_stream.hip: frame-pair
-// streaming).  Not installed; include/me.h is the public interface.
+// (me_api.hip: single-frame and stripe entry points, make_args, check_stripe,
+// attach_scratch and launch_ordered; me_stream.hip: frame-pair streaming).
+// Not installed; include/me.h is the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -134,9 +135,15 @@ me_status own_stream(me_ctx* c, Dev& d);
 me_status grow(me_ctx* c, void** p, size_t* cap, size_t need);
 me_status check_args(me_ctx* c, const void* ref, const void* cur, int width, int height,
                      int stride, int blk, int range, int cost, const void* mv);
-SearchArgs make_args(const uint8_t* ref, int ref_row0, const uint8_t* cur, int cur_row0,
-                     int width, int height, int stride, int blk, int range, int cost, int r0,
-                     int r1, int16_t* mv, uint32_t* cst);
+// The arguments of job J's search of a frame (job_args over the geometry; no
+// context buffers yet: attach_scratch).  The base of a job list is job 0's.
+SearchArgs make_args(const SearchJob& J, int width, int height, int stride, int blk, int range,
+                     int cost);
+// A stripe's block rows [r0, r1) of nby and its planes' first rows against the
+// stripe contract (include/me.h): ME_EINVAL and the message, prefixed with
+// "job <job>: " for job >= 0 (a job list), or ME_OK.
+me_status check_stripe(me_ctx* c, int nby, int blk, int range, int r0, int r1, int ref_row0,
+                       int cur_row0, int job);
 
 // Point p at d's search scratch, growing it to what p's search needs.  A
 // device's scratch serves one search at a time: launch searches that use it
@@ -147,18 +154,15 @@ SearchArgs make_args(const uint8_t* ref, int ref_row0, const uint8_t* cur, int c
 // (mfma_batch_scratch), else for one search
 me_status attach_scratch(me_ctx* c, Dev& d, SearchArgs& p, bool cap = false, int batch = 1);
 
-// Launch p (scratch attached) on stream s after every earlier search of d:
-// a search arriving on a different stream than the previous one first waits
-// for that search's end event.  A failed launch re-zeroes the self-resetting
-// tile counters and merge buffers (a partly run kernel may have left them
-// dirty) before returning ME_EDEVICE.
-me_status launch_ordered(me_ctx* c, Dev& d, SearchArgs& p, hipStream_t s);
-
-// The same for a job table (launch_jobs): jobs share base's geometry, cost and
-// scratch (attach_scratch(base, cap, n) for equal jobs).  cap: being captured
-// (no ordering, no state change).
-me_status launch_jobs_ordered(me_ctx* c, Dev& d, const SearchArgs& base, const SearchJob* jobs,
-                              int n, hipStream_t s, bool cap = false);
+// Launch jobs [0, n) (launch_jobs: they share base's geometry, cost and
+// scratch; attach_scratch(base, cap, n) for equal jobs; one job for a single
+// search) on stream s after every earlier search of d: a search arriving on a
+// different stream than the previous one first waits for that search's end
+// event.  A failed launch re-zeroes the self-resetting tile counters and
+// merge buffers (a partly run kernel may have left them dirty) before
+// returning ME_EDEVICE.  cap: being captured (no ordering, no state change).
+me_status launch_ordered(me_ctx* c, Dev& d, const SearchArgs& base, const SearchJob* jobs, int n,
+                         hipStream_t s, bool cap = false);
 
 // Order stream s after the device's previous search (a stream switch) and
 // make s the device's search stream; `launch` then enqueues on s.

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "me_dispatch.h"
 #include "me_geom.h"
 #include "me_mfma_geom.h"
 
@@ -36,27 +37,26 @@ __device__ __forceinline__ void store_mv(int16_t* mv, int out, unsigned long lon
   }
 }
 
-// Search every job (geometry, cost and scratch from base): SAD jobs the flow
-// kernel takes share one launch (up to MAX_JOBS jobs), VALU jobs of the item
-// kernel likewise, everything else runs job by job through launch_search.
+// Search every job (geometry, cost and context buffers from base): asks the
+// dispatcher (me_dispatch.cpp) which kernel family takes which blocks and
+// walks its launch list.  A single search is a list of one job.
 hipError_t launch_jobs(const SearchArgs& base, const SearchJob* jobs, int n, hipStream_t stream);
 
 // Matrix-core SSD path (me_mfma.hip, me_band.hip).  MfmaGeom, MfmaJobs and the
 // planners are in me_mfma_geom.h / me_mfma_plan.cpp (host-only, pure); the
-// wrappers below read kernel_path(), tuning() and cu_count() once, call them
-// and bind the plan's device pointers from p (scratch, merge buffers).
+// sizing wrappers below read kernel_path(), tuning() and cu_count() once and
+// call them for the context (attach_scratch).
 size_t mfma_merge_tiles(const SearchArgs& p);  // tiles the merge buffers must cover
-bool plan_mfma_ssd(const SearchArgs& p, MfmaGeom* g);
-hipError_t launch_mfma_ssd(const SearchArgs& p, const MfmaGeom& g, hipStream_t stream);
 size_t mfma_ssd_scratch(const SearchArgs& p);  // 0: path not applicable
 // Scratch for n equal-geometry jobs of p's shape in batched launches (at most
 // MAX_JOBS per launch, capped near 1 GiB), never less than mfma_ssd_scratch(p):
 // plan_mfma_batch's need.
 size_t mfma_batch_scratch(const SearchArgs& p, int n);
-// Equal-geometry SSD jobs as plan_mfma_batch plans them for the scratch of
-// base.  False (nothing launched): they run job by job.
-bool launch_mfma_jobs(const SearchArgs& base, const SearchJob* jobs, int n, hipStream_t stream,
-                      hipError_t* err);
+// Every kernel of the plan g (a dispatcher's MFMA launch) over the n
+// equal-geometry jobs at `jobs`, job j's prepass planes at base.scratch + j *
+// scratch_stride: binds g's pointers from base and fills the job table.
+hipError_t launch_mfma(const SearchArgs& base, const SearchJob* jobs, int n, MfmaGeom g,
+                       size_t scratch_stride, hipStream_t stream);
 // Band-walk kernel (me_band.hip): launch every job of jb on the plan g.
 hipError_t launch_bw(const SearchArgs& p, const MfmaGeom& g, const MfmaJobs& jb, hipStream_t stream);
 // Tiles of cross-workgroup merge buffers (mkeys: 16 u64 keys each, ~0; mcnt:
@@ -64,7 +64,6 @@ hipError_t launch_bw(const SearchArgs& p, const MfmaGeom& g, const MfmaJobs& jb,
 size_t merge_tiles_needed(const SearchArgs& p);
 bool mfma_disabled();
 
-hipError_t launch_search(const SearchArgs& p, hipStream_t stream, int* used_fast);
 // Records the kernel family of a search being launched (ME_SEARCH_PATH_*):
 // process-wide (me_last_search_path) and, inside a PathScope, for the
 // context device the search runs on (me_ctx_last_search_path).

@@ -1743,51 +1743,12 @@ static hipError_t launch_fast(const SearchArgs& p, const QsadGeom& g, int K, con
   return hipErrorInvalidValue;
 }
 
-// Plans depend only on the search shape: cache them (process-wide, under a
-// mutex: the per-device threads of multi_search and me_search_pairs share
-// them) so a steady stream of same-shape searches pays the planner once.
-// One ring of 8 per planner (me_valu_plan.cpp).
-enum PlanKind { PLAN_ITEM = 0, PLAN_FLOW = 1 };
-
-// The plan of `kind` for `rows` block rows of p's shape on planes of
-// alignment class ac (align_class; of every job of a batch).  K may be null.
-static bool cached_plan(PlanKind kind, const SearchArgs& p, int rows, int ac, QsadGeom* g, int* K) {
-  constexpr int N = 8;
-  struct Entry { PlanShape key; bool ok; QsadGeom g; int K; };
-  static struct { Entry e[N]; int used, next; } rings[2];
-  static std::mutex mu;
-  // what each planner reads of the class: the item kernel nothing of cur's
-  // 16-byte alignment, the flow kernel only whether everything is 16-byte aligned
-  const int all16 = ALIGN_REF16 | ALIGN_CUR16;
-  const int align = kind == PLAN_ITEM ? ac & (ALIGN_4 | ALIGN_REF16) : (ac & all16) == all16 ? ALIGN_ALL : 0;
-  const PlanShape key{p.width, p.height, p.stride, p.blk, p.range, p.cost_kind, rows, align};
-  auto& ring = rings[kind];
-  std::lock_guard<std::mutex> lk(mu);
-  const Entry* hit = nullptr;
-  for (int i = 0; i < ring.used && !hit; i++)
-    if (ring.e[i].key == key) hit = &ring.e[i];
-  if (!hit) {
-    Entry& e = ring.e[ring.next];
-    e.key = key;
-    e.K = 13;
-    e.ok = kind == PLAN_ITEM ? plan_fast(key, cu_count(), tuning(), &e.g, &e.K)
-                             : plan_flow(key, cu_count(), tuning(), &e.g);
-    ring.next = (ring.next + 1) % N;
-    if (ring.used < N) ring.used++;
-    hit = &e;
-  }
-  *g = hit->g;
-  if (K) *K = hit->K;
-  return hit->ok;
-}
-
 // The job table of jobs [0, n) (n <= MAX_JOBS; rows [r0, r1) each, already
 // cut to what the kernel takes), wg_per_row tiles per block row.
 static FlowJobs job_table(const SearchArgs& p, int wg_per_row, const SearchJob* jobs, int n) {
   FlowJobs jb;
   jb.n = 0;
   jb.tile_pre[0] = 0;
-  const int B = p.blk, S = p.range, H = p.height;
   for (int i = 0; i < n; i++) {
     const SearchJob& J = jobs[i];
     if (J.r1 <= J.r0) continue;
@@ -1795,8 +1756,9 @@ static FlowJobs job_table(const SearchArgs& p, int wg_per_row, const SearchJob* 
     jb.r0[j] = J.r0;
     jb.ref_row0[j] = J.ref_row0;
     jb.cur_row0[j] = J.cur_row0;
-    jb.ref_bytes[j] = ref_resident_bytes(J.r1, B, S, H, J.ref_row0, p.stride, p.width);
-    jb.cur_bytes[j] = cur_resident_bytes(J.r1, B, H, J.cur_row0, p.stride, p.width);
+    const SearchArgs q = job_args(p, J);
+    jb.ref_bytes[j] = q.ref_bytes;
+    jb.cur_bytes[j] = q.cur_bytes;
     jb.ref[j] = J.ref;
     jb.cur[j] = J.cur;
     jb.mv[j] = J.mv;
@@ -1835,221 +1797,57 @@ size_t merge_tiles_needed(const SearchArgs& p) {
   return p.cost_kind == COST_SSD ? mfma_merge_tiles(p) : 0;
 }
 
-// The single-job arguments of job J (geometry, cost and scratch from base).
-static SearchArgs job_args(const SearchArgs& base, const SearchJob& J) {
-  SearchArgs q = base;
-  q.ref = J.ref;
-  q.ref_row0 = J.ref_row0;
-  q.cur = J.cur;
-  q.cur_row0 = J.cur_row0;
-  q.block_row_begin = J.r0;
-  q.block_row_end = J.r1;
-  q.mv = J.mv;
-  q.cost = J.cost;
-  q.ref_bytes = ref_resident_bytes(J.r1, base.blk, base.range, base.height, J.ref_row0, base.stride,
-                                   base.width);
-  q.cur_bytes = cur_resident_bytes(J.r1, base.blk, base.height, J.cur_row0, base.stride, base.width);
-  return q;
-}
-
-// End of the full-height (and h = B/2) rows of [.., r1) the qsad bodies take;
-// a bottom row of another height goes to the generic kernel.
-static int qsad_rows_end(const SearchArgs& p, int r1) {
-  const int nby = (p.height + p.blk - 1) / p.blk;
-  const int h_last = p.height - (nby - 1) * p.blk;
-  return r1 == nby && h_last != p.blk && h_last != p.blk / 2 ? r1 - 1 : r1;
-}
-
-// The rows and columns of job J that a qsad kernel planned with nbx_full full
-// blocks per row leaves (a bottom row of another height, the partial right
-// column): the generic kernel.
-static hipError_t launch_leftovers(const SearchArgs& base, const SearchJob& J, int nbx_full,
-                                   hipStream_t stream) {
-  const int rq1 = qsad_rows_end(base, J.r1);
-  if (rq1 == J.r1 && nbx_full >= base.nbx) return hipSuccess;  // nothing left: the usual case
-  const SearchArgs q = job_args(base, J);
-  if (rq1 < J.r1) {
-    const hipError_t e = launch_generic(q, 0, nbx_full, rq1, J.r1 - rq1, stream);
-    if (e != hipSuccess) return e;
+// One launch of the dispatcher's list (me_dispatch.h).
+static hipError_t run_launch(const SearchArgs& base, const SearchJob* jobs, const Launch& l,
+                             hipStream_t stream) {
+  if (l.path) note_path(l.path);
+  const SearchJob& J = jobs[l.job0];
+  switch (l.kind) {
+    case LAUNCH_GENERIC:
+      return launch_generic(job_args(base, J), l.bx0, l.bx1 - l.bx0, launch_r0(l, J),
+                            launch_r1(l, J) - launch_r0(l, J), stream);
+    case LAUNCH_SSIM:
+      return launch_ssim(job_args(base, J), stream);
+    case LAUNCH_MFMA:
+      return launch_mfma(base, &J, l.njobs, l.mg, l.scratch_stride, stream);
   }
-  if (nbx_full < base.nbx)
-    return launch_generic(q, nbx_full, base.nbx - nbx_full, J.r0, J.r1 - J.r0, stream);
-  return hipSuccess;
-}
-
-// The persistent item kernel (and the generic kernel for what it leaves).
-static hipError_t launch_items(const SearchArgs& p, hipStream_t stream, int* used_fast) {
-  const int r0 = p.block_row_begin, r1 = p.block_row_end;
-  QsadGeom g;
-  int K = 0;
-  if (!cached_plan(PLAN_ITEM, p, r1 - r0, align_class(p.stride, p.ref, p.cur), &g, &K))
-    return launch_generic(p, 0, p.nbx, r0, r1 - r0, stream);
-  SearchJob J{p.ref, p.ref_row0, p.cur, p.cur_row0, r0, qsad_rows_end(p, r1), p.mv, p.cost};
-  const hipError_t e = launch_fast(p, g, K, job_table(p, g.wg_per_row, &J, 1), stream);
-  if (e != hipSuccess) return e;
-  if (used_fast) *used_fast = 1;
-  J.r1 = r1;
-  return launch_leftovers(p, J, g.nbx_full, stream);
-}
-
-// SAD jobs on the flow kernel where its plan (over every job's rows) takes
-// them, all in one launch (MAX_JOBS jobs per launch).  Past the LDS ring a
-// slot is refilled when its item's last wave-task ends; with the fairness
-// check in the kernel (QsadGeom::fair) that wave-task no longer lags, and one
-// launch of 8 1080p frames takes 62.5-63 us per frame against 71.4 for
-// back-to-back single-frame launches on the same box (without the check:
-// 80.9 us, waves spinning on unpublished slots; profiles/r03ac_fair_sweep.jsonl).
-// Tuning build: ME_FLOW_ONE=0 cuts a batch into launches of about one ring.
-// Returns false (nothing launched) when the flow kernel does not apply.
-static bool launch_flow_jobs(const SearchArgs& base, const SearchJob* jobs, int n, hipStream_t stream,
-                             hipError_t* err) {
-  *err = hipSuccess;
-  if (base.cost_kind != COST_SAD || n < 1) return false;
-  int rows = 0;  // the planner counts tiles over every job's rows
-  for (int i = 0; i < n; i++) {
-    rows += jobs[i].r1 - jobs[i].r0;
-    if ((uintptr_t)jobs[i].ref % 16 || (uintptr_t)jobs[i].cur % 16) return false;
-  }
-  QsadGeom g;
-  if (!cached_plan(PLAN_FLOW, base, rows, align_class(base.stride, jobs[0].ref, jobs[0].cur), &g, nullptr))
-    return false;
-  long total = 0;
-  for (int i = 0; i < n; i++)
-    total += (long)g.wg_per_row * (qsad_rows_end(base, jobs[i].r1) - jobs[i].r0);
-  const long ring = tuning().flow_one != 0 ? (1L << 40) : (long)g.flow_slots * cu_count();
-  const long nl = (total + ring - 1) / ring;  // launches of about total / nl tiles
-  const long target = nl > 1 ? (total + nl - 1) / nl : total;
+  // ITEM, FLOW: the launch's rows of every job, its records from their first row
   SearchJob fj[MAX_JOBS];
-  int m = 0;
-  long tiles = 0;
-  for (int i = 0; i < n && *err == hipSuccess; i++) {
-    SearchJob J = jobs[i];
-    J.r1 = qsad_rows_end(base, J.r1);
-    const long t = (long)g.wg_per_row * (J.r1 - J.r0);
-    if (m && (tiles + t > target || m == MAX_JOBS)) {
-      *err = launch_flow(base, g, fj, m, stream);
-      m = 0;
-      tiles = 0;
-    }
-    fj[m++] = J;
-    tiles += t;
+  for (int i = 0; i < l.njobs; i++) {
+    fj[i] = jobs[l.job0 + i];
+    const int skip = launch_r0(l, fj[i]) - fj[i].r0;
+    fj[i].r0 += skip;
+    fj[i].r1 = launch_r1(l, fj[i]);
+    fj[i].mv += 2 * (size_t)skip * base.nbx;
+    if (fj[i].cost) fj[i].cost += (size_t)skip * base.nbx;
   }
-  if (m && *err == hipSuccess) *err = launch_flow(base, g, fj, m, stream);
-  // the rows and columns the flow kernel leaves, job by job
-  for (int i = 0; i < n && *err == hipSuccess; i++)
-    *err = launch_leftovers(base, jobs[i], g.nbx_full, stream);
-  return true;
-}
-
-// VALU jobs the item kernel takes (SAD, or SSD off the matrix cores) in one
-// launch per MAX_JOBS: per-job launches each paid the persistent grid's fill
-// and drain (8 stripes of a 4K frame: 1.165 ms against 1.047 for the frame).
-// Returns false (nothing launched) when the jobs' planes differ in alignment
-// class or the item kernel does not take the shape.
-static bool launch_item_jobs(const SearchArgs& base, const SearchJob* jobs, int n,
-                             hipStream_t stream, hipError_t* err) {
-  *err = hipSuccess;
-  if (n < 2 || (base.cost_kind != COST_SAD && base.cost_kind != COST_SSD)) return false;
-  // (the item planner reads nothing of cur's 16-byte alignment)
-  const int item_bits = ALIGN_4 | ALIGN_REF16;
-  const int ac = align_class(base.stride, jobs[0].ref, jobs[0].cur) & item_bits;
-  int rows = 0;  // the planner counts tiles over every job's rows
-  for (int i = 0; i < n; i++) {
-    rows += jobs[i].r1 - jobs[i].r0;
-    if ((align_class(base.stride, jobs[i].ref, jobs[i].cur) & item_bits) != ac) return false;
-  }
-  QsadGeom g;
-  int K = 0;
-  if (!cached_plan(PLAN_ITEM, base, rows, ac, &g, &K)) return false;
-  // Every job shares the launch, however large: with whole frames per XCD band
-  // the bands need no halo rows.  8K 8x8 +-128, 16 frames: 17.09 ms and 70.7 MB
-  // read per frame in one row-major launch, against 17.26 ms and 89.9 MB one
-  // launch per frame (profiles/r04m_variants_8k.txt; round 3 measured the
-  // opposite, 124 vs 98 MB, with tiles claimed two ahead).  Row-major: the
-  // strip walk, which keeps a single wide frame's window rows in L2, only
-  // spreads a batch's working set (same run: strips of 16 tiles 87.9 MB).
-  const int per = tuning().item_batch == 0 ? 1 : MAX_JOBS;  // tuning build: ME_ITEM_BATCH=0
-  if (n > 1 && tuning().strip < 0) g.strip_w = 0;
-  for (int i0 = 0; i0 < n && *err == hipSuccess; i0 += per) {
-    const int m = n - i0 < per ? n - i0 : per;
-    SearchJob fj[MAX_JOBS];
-    for (int i = 0; i < m; i++) {
-      fj[i] = jobs[i0 + i];
-      fj[i].r1 = qsad_rows_end(base, fj[i].r1);
-    }
-    *err = launch_fast(base, g, K, job_table(base, g.wg_per_row, fj, m), stream);
-  }
-  // the rows and columns the item kernel leaves, job by job
-  for (int i = 0; i < n && *err == hipSuccess; i++)
-    *err = launch_leftovers(base, jobs[i], g.nbx_full, stream);
-  return true;
-}
-
-static hipError_t launch_valu(const SearchArgs& p, hipStream_t stream, int* used_fast) {
-  note_path(1);
-  if (p.block_row_end <= p.block_row_begin) return hipSuccess;
-  const SearchJob J{p.ref, p.ref_row0, p.cur, p.cur_row0, p.block_row_begin, p.block_row_end, p.mv, p.cost};
-  hipError_t e;
-  if (launch_flow_jobs(p, &J, 1, stream, &e)) {
-    if (used_fast) *used_fast = 3;
-    return e;
-  }
-  return launch_items(p, stream, used_fast);
+  if (l.kind == LAUNCH_FLOW) return launch_flow(base, l.g, fj, l.njobs, stream);
+  return launch_fast(base, l.g, l.K, job_table(base, l.g.wg_per_row, fj, l.njobs), stream);
 }
 
 hipError_t launch_jobs(const SearchArgs& base, const SearchJob* jobs, int n, hipStream_t stream) {
-  hipError_t e;
-  if (n > 1 && launch_flow_jobs(base, jobs, n, stream, &e)) {
-    note_path(1);
+  const SearchShape s{base.width, base.height, base.stride, base.blk, base.range, base.cost_kind,
+                      base.mkeys && base.mcnt ? base.merge_tiles : 0,
+                      base.scratch ? base.scratch_bytes : 0};
+  constexpr int CAP = 64;  // (longer batch lists come in windows)
+  static_assert(CAP >= DISPATCH_JOB_MAX, "a job's launches fit the array");
+  Launch list[CAP];
+  auto run = [&](int count) {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < count && e == hipSuccess; i++) e = run_launch(base, jobs, list[i], stream);
     return e;
+  };
+  for (int skip = 0;; skip += CAP) {
+    const int total = dispatch_batch(s, jobs, n, kernel_path(), cu_count(), tuning(), skip, list, CAP);
+    if (total < 0) break;  // job by job
+    const hipError_t e = run(total - skip < CAP ? total - skip : CAP);
+    if (e != hipSuccess || total - skip <= CAP) return e;
   }
-  // SSD jobs of one geometry share the matrix cores' launches (prepass planes
-  // per job in the context scratch); others go one by one
-  if (n > 1 && launch_mfma_jobs(base, jobs, n, stream, &e)) return e;
-  MfmaGeom mg;
-  const bool mfma = base.cost_kind == COST_SSD && plan_mfma_ssd(job_args(base, jobs[0]), &mg) &&
-                    (mg.scratch_bytes == 0 || base.scratch);
-  if (n > 1 && !mfma && launch_item_jobs(base, jobs, n, stream, &e)) {
-    note_path(1);
-    return e;
-  }
-  for (int i = 0; i < n; i++) {
-    if (jobs[i].r1 <= jobs[i].r0) continue;
-    e = launch_search(job_args(base, jobs[i]), stream, nullptr);
+  for (int j = 0; j < n; j++) {
+    const hipError_t e = run(dispatch_job(s, jobs, j, kernel_path(), cu_count(), tuning(), list));
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
-}
-
-hipError_t launch_search(const SearchArgs& p, hipStream_t stream, int* used_fast) {
-  const int r0 = p.block_row_begin, r1 = p.block_row_end;
-  if (r1 <= r0) return hipSuccess;
-  if (used_fast) *used_fast = 0;
-  if (p.cost_kind == COST_SSIM) return launch_ssim(p, stream);
-  MfmaGeom mg;
-  // (the band-walk and lean kernels need no context scratch: scratch_bytes 0)
-  if (p.cost_kind == COST_SSD && plan_mfma_ssd(p, &mg) &&
-      (mg.scratch_bytes == 0 || (p.scratch && p.scratch_bytes >= mg.scratch_bytes))) {
-    // Matrix cores: every full-width block (the partial bottom row included);
-    // the partial right column stays on the generic kernel.
-    hipError_t e = launch_mfma_ssd(p, mg, stream);
-    if (e != hipSuccess) return e;
-    if (used_fast) *used_fast = 2;
-    const int rest = mg.row0 + mg.nrows;  // < r1: a partial bottom row the MFMA kernel left (B = 8)
-    if (mg.nbx < p.nbx) {
-      e = launch_generic(p, mg.nbx, p.nbx - mg.nbx, r0, rest - r0, stream);
-      if (e != hipSuccess) return e;
-    }
-    if (rest < r1) {
-      SearchArgs q = p;
-      q.block_row_begin = rest;
-      q.mv = p.mv + 2 * (size_t)(rest - r0) * p.nbx;
-      if (p.cost) q.cost = p.cost + (size_t)(rest - r0) * p.nbx;
-      return launch_valu(q, stream, nullptr);
-    }
-    return hipSuccess;
-  }
-  return launch_valu(p, stream, used_fast);
 }
 
 }  // namespace me

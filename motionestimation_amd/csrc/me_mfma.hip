@@ -1809,29 +1809,18 @@ static void bind(const SearchArgs& p, MfmaGeom* g) {
 
 size_t mfma_merge_tiles(const SearchArgs& p) { return mfma_merge_tiles(shape_of(p)); }
 
-bool plan_mfma_ssd(const SearchArgs& p, MfmaGeom* g) {
-  if (!plan_mfma_ssd(shape_of(p), kernel_path(), cu_count(), tuning(), g)) return false;
-  bind(p, g);
-  return true;
-}
-
 // Scratch bytes the MFMA path needs for this search (0: path not applicable).
 size_t mfma_ssd_scratch(const SearchArgs& p) {
   MfmaGeom g;
-  return plan_mfma_ssd(p, &g) ? g.scratch_bytes : 0;
+  return plan_mfma_ssd(shape_of(p), kernel_path(), cu_count(), tuning(), &g) ? g.scratch_bytes : 0;
 }
 
-// The one-job table of a single search (its own pointers, its own scratch).
-static MfmaJobs single_job(const SearchArgs& p, const MfmaGeom& g) {
-  MfmaJobs jb;
-  jb.n = 1;
-  jb.wgs = wgs_per_job(g);
-  jb.scratch_stride = 0;
-  jb.ref[0] = p.ref;
-  jb.cur[0] = p.cur;
-  jb.mv[0] = p.mv;
-  jb.cost[0] = p.cost;
-  return jb;
+// plan_mfma_batch (me_mfma_plan.cpp) decides how n equal jobs run: the
+// context sizes its scratch with it, the dispatcher plans the launches.
+size_t mfma_batch_scratch(const SearchArgs& p, int n) {
+  MfmaBatch b;
+  plan_mfma_batch(shape_of(p), n, MFMA_SCRATCH_UNLIMITED, kernel_path(), cu_count(), tuning(), &b);
+  return b.need;
 }
 
 // Prepass over every job of the table (grid z = job).
@@ -1886,17 +1875,26 @@ static hipError_t launch_bw_jobs(const SearchArgs& p, const MfmaGeom& g, const M
   return launch_bmv(p, t, tj, stream);
 }
 
-static int mfma_path(const SearchArgs& p, const MfmaGeom& g) {
-  return g.bw ? 3 : g.bmv ? 4 : p.blk == 8 ? 6 : g.bm ? 2 : 5;
-}
-
-hipError_t launch_mfma_ssd(const SearchArgs& p, const MfmaGeom& g, hipStream_t stream) {
-  note_path(mfma_path(p, g));
-  const MfmaJobs jb = single_job(p, g);
+hipError_t launch_mfma(const SearchArgs& base, const SearchJob* jobs, int n, MfmaGeom g,
+                       size_t scratch_stride, hipStream_t stream) {
+  const SearchArgs p = job_args(base, jobs[0]);  // (what the jobs share; the tile kernels' one job)
+  bind(p, &g);
+  MfmaJobs jb;
+  jb.n = n;
+  jb.wgs = wgs_per_job(g);
+  jb.scratch_stride = scratch_stride;
+  for (int j = 0; j < n; j++) {
+    jb.ref[j] = jobs[j].ref;
+    jb.cur[j] = jobs[j].cur;
+    jb.mv[j] = jobs[j].mv;
+    jb.cost[j] = jobs[j].cost;
+  }
   if (g.bw) return launch_bw_jobs(p, g, jb, stream);
   if (g.bmv) return launch_bmv(p, g, jb, stream);
   hipError_t e = launch_prep(p, g, jb, stream);
   if (e != hipSuccess) return e;
+  if (g.bm) return launch_bm16(p, g, jb, stream);
+  // the tile kernels: one job (plan_mfma_batch batches the block-major plans only)
   if (p.blk == 8) {
     const dim3 grid8((unsigned)((g.tiles_x + ME_SSD8_NT - 1) / ME_SSD8_NT * g.tiles_y));
     e = lds_attr((const void*)me_mfma_ssd8_kernel<ME_SSD8_KM>, g.lds);
@@ -1904,7 +1902,6 @@ hipError_t launch_mfma_ssd(const SearchArgs& p, const MfmaGeom& g, hipStream_t s
     hipLaunchKernelGGL(me_mfma_ssd8_kernel<ME_SSD8_KM>, grid8, dim3(256), g.lds, stream, p, g);
     return hipGetLastError();
   }
-  if (g.bm) return launch_bm16(p, g, jb, stream);
   const int wpt = (g.ngx + g.ngxw - 1) / g.ngxw;
   const dim3 grid((unsigned)(g.tiles_x * g.tiles_y * wpt));
 #define ME_MFMA_CASE(NG, KK)                                                              \
@@ -1917,69 +1914,6 @@ hipError_t launch_mfma_ssd(const SearchArgs& p, const MfmaGeom& g, hipStream_t s
   ME_MFMA_CASE(1, 2) ME_MFMA_CASE(1, 3) ME_MFMA_CASE(2, 2) ME_MFMA_CASE(2, 3)
 #undef ME_MFMA_CASE
   return hipErrorInvalidValue;
-}
-
-// ------------------------------------------------------------------ batches
-// plan_mfma_batch (me_mfma_plan.cpp) decides how n equal jobs run: the
-// context sizes its scratch with it, the launcher launches what it planned.
-size_t mfma_batch_scratch(const SearchArgs& p, int n) {
-  MfmaBatch b;
-  plan_mfma_batch(shape_of(p), n, MFMA_SCRATCH_UNLIMITED, kernel_path(), cu_count(), tuning(), &b);
-  return b.need;
-}
-
-bool launch_mfma_jobs(const SearchArgs& base, const SearchJob* jobs, int n, hipStream_t stream,
-                      hipError_t* err) {
-  *err = hipSuccess;
-  if (n < 2) return false;
-  for (int i = 1; i < n; i++)  // one geometry: the same rows of same-sized frames
-    if (jobs[i].r0 != jobs[0].r0 || jobs[i].r1 != jobs[0].r1 ||
-        jobs[i].ref_row0 != jobs[0].ref_row0 || jobs[i].cur_row0 != jobs[0].cur_row0)
-      return false;
-  SearchArgs p = base;
-  p.ref = jobs[0].ref;
-  p.ref_row0 = jobs[0].ref_row0;
-  p.cur = jobs[0].cur;
-  p.cur_row0 = jobs[0].cur_row0;
-  p.block_row_begin = jobs[0].r0;
-  p.block_row_end = jobs[0].r1;
-  p.mv = jobs[0].mv;
-  p.cost = jobs[0].cost;
-  MfmaBatch b;
-  if (!plan_mfma_batch(shape_of(p), n, p.scratch ? p.scratch_bytes : 0, kernel_path(), cu_count(),
-                       tuning(), &b) || b.jobs < 2)
-    return false;
-  const MfmaGeom& g = b.g;
-  // the plan saw job 0's pointers only: every job's planes must meet the same
-  // alignment (4-byte DMA sources; the block-major kernel's 16-byte cur row
-  // loads), else the batch runs job by job, each planned on its own
-  const int need = ALIGN_4 | (g.bm ? ALIGN_CUR16 : 0);
-  for (int i = 1; i < n; i++)
-    if ((align_class(p.stride, jobs[i].ref, jobs[i].cur) & need) != need) return false;
-  bind(p, &b.g);
-  note_path(mfma_path(p, g));
-  for (int i0 = 0; i0 < n && *err == hipSuccess; i0 += b.jobs) {
-    MfmaJobs jb;
-    jb.n = n - i0 < b.jobs ? n - i0 : b.jobs;
-    jb.wgs = wgs_per_job(g);
-    jb.scratch_stride = b.stride;
-    for (int j = 0; j < jb.n; j++) {
-      const SearchJob& J = jobs[i0 + j];
-      jb.ref[j] = J.ref;
-      jb.cur[j] = J.cur;
-      jb.mv[j] = J.mv;
-      jb.cost[j] = J.cost;
-    }
-    if (g.bw) {
-      *err = launch_bw_jobs(p, g, jb, stream);
-    } else if (g.bmv) {
-      *err = launch_bmv(p, g, jb, stream);
-    } else {
-      *err = launch_prep(p, g, jb, stream);
-      if (*err == hipSuccess) *err = launch_bm16(p, g, jb, stream);
-    }
-  }
-  return true;
 }
 
 }  // namespace me

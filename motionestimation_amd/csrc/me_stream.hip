@@ -458,10 +458,8 @@ me_status run_pairs(me_ctx* c, Dev& d, const Job& j, int p0, int p1) {
     for (int n = n0; n < n1; n++) {
       const int sr = slot_of[j.pairs[2 * n]], sc = slot_of[j.pairs[2 * n + 1]];
       const size_t o = (size_t)(n - p0) * nb;
-      if (n == n0)
-        base = make_args(d.slots[sr], 0, d.slots[sc], 0, W, H, W, B, j.range, j.cost, 0, nby,
-                         out_mv + 2 * o, out_cost + o);
       jobs.push_back(SearchJob{d.slots[sr], 0, d.slots[sc], 0, 0, nby, out_mv + 2 * o, out_cost + o});
+      if (n == n0) base = make_args(jobs[0], W, H, W, B, j.range, j.cost);
     }
     // this batch's uploads: a wait packet only if they have not landed yet
     if (has_upl[batch]) {
@@ -472,7 +470,7 @@ me_status run_pairs(me_ctx* c, Dev& d, const Job& j, int p0, int p1) {
         return fail(c, ME_EDEVICE, "upload event: %s", hipGetErrorString(q));
     }
     if ((s = me::attach_scratch(c, d, base, false, n1 - n0)) != ME_OK) return s;
-    if ((s = me::launch_jobs_ordered(c, d, base, jobs.data(), n1 - n0, d.stream)) != ME_OK) return s;
+    if ((s = me::launch_ordered(c, d, base, jobs.data(), n1 - n0, d.stream)) != ME_OK) return s;
     HIPCHK(c, hipEventRecord(d.batch_ev[batch % kEvRing], d.stream));
     ranges.emplace_back(n0, n1);
     // then the next batch's uploads (after the launch: pageable frames' host

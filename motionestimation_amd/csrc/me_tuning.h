@@ -78,7 +78,7 @@ int path_code_of(int me_path_value);  // ME_PATH_* -> code above (-1 if invalid)
 // While alive on a thread: kernel_path() returns `path` when it is >= 0, and
 // note_path() also stores into *last (the context device's last search path).
 // Set around the planning and launch of a context's search (attach_scratch,
-// launch_ordered, launch_jobs_ordered); nests.
+// launch_ordered); nests.
 struct PathScope {
   PathScope(int path, std::atomic<int>* last);
   ~PathScope();

@@ -6,8 +6,13 @@
 // Both are pure functions of the shape, the alignment class of the planes, the
 // CU count and the tuning overrides: no device query, no statics, so the CPU
 // tests pin their plans (tests/test_valu_plan.py) and run them under the
-// sanitizers (oracle/san_main.cc).  me_kernels.hip caches and launches them.
+// sanitizers (oracle/san_main.cc).  cached_plan, at the end, is the plan cache
+// the dispatcher (me_dispatch.cpp) asks; me_kernels.hip launches the plans.
 #include <stdint.h>
+#include <string.h>
+
+#include <mutex>
+#include <type_traits>
 
 #include "me_geom.h"
 #include "me_tuning.h"
@@ -387,6 +392,39 @@ bool plan_flow(const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g) {
     }
   }
   return true;
+}
+
+bool cached_plan(PlanKind kind, const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g, int* K) {
+  constexpr int N = 8;
+  struct Entry { PlanShape key; int cus; Tuning tu; bool ok; QsadGeom g; int K; };
+  static struct { Entry e[N]; int used, next; } rings[2];
+  static std::mutex mu;
+  static_assert(std::has_unique_object_representations<Tuning>::value, "Tuning compared bytewise");
+  // what each planner reads of the class: the item kernel nothing of cur's
+  // 16-byte alignment, the flow kernel only whether everything is 16-byte aligned
+  const int all16 = ALIGN_REF16 | ALIGN_CUR16;
+  PlanShape key = s;
+  key.align = kind == PLAN_ITEM ? s.align & (ALIGN_4 | ALIGN_REF16) : (s.align & all16) == all16 ? ALIGN_ALL : 0;
+  auto& ring = rings[kind];
+  std::lock_guard<std::mutex> lk(mu);
+  const Entry* hit = nullptr;
+  for (int i = 0; i < ring.used && !hit; i++)
+    if (ring.e[i].key == key && ring.e[i].cus == cus && memcmp(&ring.e[i].tu, &tu, sizeof tu) == 0)
+      hit = &ring.e[i];
+  if (!hit) {
+    Entry& e = ring.e[ring.next];
+    e.key = key;
+    e.cus = cus;
+    e.tu = tu;
+    e.K = 13;
+    e.ok = kind == PLAN_ITEM ? plan_fast(key, cus, tu, &e.g, &e.K) : plan_flow(key, cus, tu, &e.g);
+    ring.next = (ring.next + 1) % N;
+    if (ring.used < N) ring.used++;
+    hit = &e;
+  }
+  *g = hit->g;
+  if (K) *K = hit->K;
+  return hit->ok;
 }
 
 }  // namespace me

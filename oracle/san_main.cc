@@ -16,7 +16,11 @@
 //   - the matrix-core SSD planners (me_mfma_plan.cpp: the single-search plan,
 //     plan_bw, the batch plan) likewise, over every kernel path: the batch's
 //     planes fit the scratch that was sized for it, LDS and plane bounds, the
-//     kernel instances the launchers dispatch, the band walk's cover.
+//     kernel instances the launchers dispatch, the band walk's cover;
+//   - the search dispatcher (me_dispatch.cpp) over the cases of
+//     tests/golden/plans/dispatch.json, from four threads at once (they share
+//     the plan cache of me_valu_plan.cpp): every block of every job in
+//     exactly one launch, through launch windows of several sizes.
 // Exit status 0 and "san ok" on success; the sanitizers abort otherwise.
 #include <stdint.h>
 #include <stdio.h>
@@ -25,8 +29,10 @@
 #include <unistd.h>
 
 #include <string>
+#include <thread>
 #include <vector>
 
+#include "dispatch_cases.h"
 #include "me.h"
 #include "me_geom.h"
 #include "me_mfma_geom.h"
@@ -417,12 +423,62 @@ static void mfma_planners() {
   CHECK(accepted > 2000 && walks > 800 && batches > 600);
 }
 
+// One pass over the dispatcher's case table: each launch's rectangles painted
+// into a grid per job; `cap` launches per dispatch call.
+static void dispatch_pass(const std::vector<std::string>& lines, int cap) {
+  const me::Tuning tu;
+  DispatchCase c;
+  int cases = 0;
+  for (const std::string& line : lines) {
+    if (!parse_dispatch_case(line.c_str(), 256, tu, &c)) continue;
+    cases++;
+    const int B = c.s.blk, nby = (c.s.height + B - 1) / B, nbx = (c.s.width + B - 1) / B;
+    const int nj = (int)c.jobs.size();
+    const std::vector<me::Launch> list = dispatch_all(c, 256, tu, cap);
+    std::vector<int> grid((size_t)nj * nby * nbx, 0);
+    for (const me::Launch& l : list) {
+      CHECK(l.kind >= me::LAUNCH_GENERIC && l.kind <= me::LAUNCH_SSIM);
+      CHECK(l.job0 >= 0 && l.njobs >= 1 && l.njobs <= me::MAX_JOBS && l.job0 + l.njobs <= nj);
+      CHECK(l.njobs == 1 || l.kind == me::LAUNCH_ITEM || l.kind == me::LAUNCH_FLOW || l.kind == me::LAUNCH_MFMA);
+      CHECK(0 <= l.bx0 && l.bx0 <= l.bx1 && l.bx1 <= nbx);
+      if (l.kind == me::LAUNCH_MFMA) {  // (the kernels cover the plan's rectangle, not the launch's)
+        CHECK((size_t)(l.njobs - 1) * l.scratch_stride + l.mg.scratch_bytes <= c.s.scratch_bytes);
+        CHECK(l.mg.row0 == l.row_lo && l.mg.row0 + l.mg.nrows == l.row_hi && l.bx0 == 0 && l.mg.nbx == l.bx1);
+      }
+      for (int j = l.job0; j < l.job0 + l.njobs; j++) {
+        const int r0 = me::launch_r0(l, c.jobs[j]), r1 = me::launch_r1(l, c.jobs[j]);
+        CHECK(r1 <= r0 || (r0 >= c.jobs[j].r0 && r1 <= c.jobs[j].r1));
+        for (int r = r0; r < r1; r++)
+          for (int bx = l.bx0; bx < l.bx1; bx++) grid[((size_t)j * nby + r) * nbx + bx]++;
+      }
+    }
+    for (int j = 0; j < nj; j++)
+      for (int r = 0; r < nby; r++)
+        for (int bx = 0; bx < nbx; bx++)
+          CHECK(grid[((size_t)j * nby + r) * nbx + bx] == (r >= c.jobs[j].r0 && r < c.jobs[j].r1 ? 1 : 0));
+  }
+  CHECK(cases > 100);
+}
+
+static void dispatcher() {
+  std::vector<std::string> lines;
+  FILE* f = fopen(DISPATCH_TABLE, "r");
+  CHECK(f != nullptr);
+  static char line[1 << 16];
+  while (fgets(line, sizeof line, f)) lines.push_back(line);
+  fclose(f);
+  std::vector<std::thread> th;
+  for (int cap : {1, 3, 64, 1024}) th.emplace_back(dispatch_pass, std::cref(lines), cap);
+  for (std::thread& t : th) t.join();
+}
+
 int main() {
   pool();
   planner();
   files();
   valu_planners();
   mfma_planners();
+  dispatcher();
   printf("san ok\n");
   return 0;
 }

@@ -66,7 +66,7 @@ def test_exact_absdiff_count():
 def test_frames_per_launch_pricing():
     """bench.py prices the roofline per launch with the library's batching rules:
     SAD batches share one launch of up to MAX_JOBS frames, 8K 8x8 +-128
-    included (me_kernels.hip launch_item_jobs); 8x8 SSD launches per frame."""
+    included (me_dispatch.cpp item_jobs); 8x8 SSD launches per frame."""
     sys.path.insert(0, REPO)
     import bench
     assert bench.sad_frames_per_launch(1920, 1080, 16, 32, 16) == 16

@@ -448,7 +448,7 @@ def test_kernel_path_reported(engine, path, want):
 
 def test_batched_ssd_partial_right_column_stays_on_mfma(engine, ssd_path):
     """A batch of 16x16 SSD frames whose width is not a multiple of 16 (854 =
-    53 x 16 + 6, rows at a 16-byte pitch of 864): launch_mfma_jobs runs it job
+    53 x 16 + 6, rows at a 16-byte pitch of 864): the dispatcher runs it job
     by job (the partial right column goes to the VALU kernels per frame), and
     the context scratch must hold one job's prepass planes for the prepass
     path -- round 5 sized it for the band-walk batch (none) and the fallback

@@ -611,7 +611,7 @@ def test_stripe_jobs_of_different_alignment_run_job_by_job(engine, cost):
     """Two jobs of one me_search_stripes_device call whose planes differ in
     alignment class (job 0's 16-byte aligned, job 1's ref one byte into a
     larger buffer) cannot share an item-kernel plan: the call falls back to
-    one search per job (launch_item_jobs -> launch_search), and each job
+    one search per job (me_dispatch.cpp: step 4 refused, step 5), and each job
     equals the oracle.  SSD on the VALU kernels, the path that plans items."""
     import torch
     w, h, stride, blk, span = 96, 64, 112, 16, 8

@@ -38,7 +38,7 @@ def _planned(c):
 
 @functools.lru_cache(maxsize=None)
 def _plans(tmpdir):
-    """{case name: plan_dump record} for the table, planned as launch_items
+    """{case name: plan_dump record} for the table, planned as the dispatcher
     plans a whole frame: rows = every block row, the class bits the item
     planner reads."""
     subprocess.run(["make", "-s", "-C", ORACLE, "plan_dump"], check=True, timeout=300)
