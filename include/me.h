@@ -346,6 +346,77 @@ me_status me_compensate_planes(me_ctx* ctx, const uint8_t* ref,
                                int block_size, const int16_t* mv_xy,
                                uint8_t* out5, double* psnr);
 
+/* ---- quarter-pel refinement and sub-pel compensation ----
+ * No reference counterpart (the reference stops at integer vectors); parity is
+ * against the numpy restatement tests/qpel_ref.py.  Exact integer arithmetic,
+ * the H.264 luma interpolation (DESIGN.md "Quarter-pel refinement" has it in
+ * full):
+ *   - a quarter-pel vector (qx, qy) is int16, four units per pixel; the
+ *     integer vector m is 4 * m.
+ *   - reference samples are EDGE REPLICATED, R(x, y) = ref[clamp(y)][clamp(x)]:
+ *     no sample is outside the frame.  This is the one deliberate difference
+ *     from the integer me_motion_compensate, which writes 0 for out-of-frame
+ *     pixels and stays as it is.
+ *   - half samples: the 6-tap (1, -5, 20, 20, -5, 1) filter, clip255((b1 + 16)
+ *     >> 5) horizontally and vertically; the centre half sample filters the
+ *     unrounded horizontal intermediates vertically, clip255((j1 + 512) >> 10).
+ *   - quarter samples: (a + b + 1) >> 1 of the two nearest half-grid samples
+ *     along the odd axis; with both axes odd, of the horizontal and the
+ *     vertical half sample among the four corners (never the pixel or the
+ *     centre half sample).
+ *   - refinement of a block (partial edge blocks keep their true size): start
+ *     at 4 * m; stage 1 tries the eight neighbours at step 2 (half-pel), stage
+ *     2 the eight at step 1 around stage 1's winner; candidates in raster
+ *     order (dy outer), a candidate wins only with a strictly smaller cost, so
+ *     ties go to the centre, then to the first candidate.  No window: the
+ *     result is within 3 quarter units of 4 * m per axis.
+ *   - ME_COST_SAD and ME_COST_SSD; ME_COST_SSIM returns ME_EUNSUPPORTED.
+ * Whole frames on one device only: a stripe would need reference rows beyond
+ * its documented cover (3 more above and below), and a multi-device context's
+ * stripes likewise, so neither is offered. */
+#define ME_QPEL_MAX_MV 8000 /* |component| of an integer input vector: 4 * m +- 3 fits int16 */
+
+/* Refine n_frames >= 1 whole frames of one geometry on HBM-resident planes of
+ * ctx's first device: frame f's planes at d_ref + f * ref_frame_stride and
+ * d_cur + f * cur_frame_stride bytes, its integer records at d_mv_xy + 2 * f *
+ * nblk, its results at d_mv_q + 2 * f * nblk and d_block_cost + f * nblk (nblk
+ * = me_num_blocks; the layout of me_full_search_batch_device).  d_block_cost
+ * may be NULL; d_mv_q == d_mv_xy (in place) is allowed.  Asynchronous on
+ * `stream`, ordered after the context's previous search like any search; uses
+ * no context scratch, so it can be captured (me_capture_begin) without a
+ * warm-up call.  Precondition: |m| <= ME_QPEL_MAX_MV per component (not
+ * checked: the field is on the device); any int16 value still reads only
+ * inside the planes, its result is then unspecified. */
+me_status me_refine_qpel_device(me_ctx* ctx, const uint8_t* d_ref, size_t ref_frame_stride,
+                                const uint8_t* d_cur, size_t cur_frame_stride, int width,
+                                int height, int stride, int block_size, me_cost cost,
+                                int n_frames, const int16_t* d_mv_xy, int16_t* d_mv_q,
+                                uint32_t* d_block_cost, void* stream);
+
+/* The same on host planes, synchronous.  mv_xy: the integer field (ME_EINVAL
+ * for a component beyond ME_QPEL_MAX_MV); mv_q: [nblocks][2] int16 quarter-pel
+ * vectors; block_cost: [nblocks] cost at mv_q (may be NULL). */
+me_status me_refine_qpel(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int width,
+                         int height, int stride, int block_size, me_cost cost,
+                         const int16_t* mv_xy, int16_t* mv_q, uint32_t* block_cost);
+
+/* me_full_search and the refinement back to back on the device: the integer
+ * field never visits the host.  One context device (ME_EUNSUPPORTED with
+ * several). */
+me_status me_full_search_qpel(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int width,
+                              int height, int stride, int block_size, int search_range,
+                              me_cost cost, int16_t* mv_q, uint32_t* block_cost);
+
+/* me_motion_compensate / me_compensate_planes with quarter-pel vectors: mc[p]
+ * is the prediction sample of p's block at that block's mv_q (edge replicated:
+ * see above); planes and PSNR are formed from mc exactly as the integer
+ * versions do. */
+me_status me_motion_compensate_qpel(me_ctx* ctx, const uint8_t* ref, int width, int height,
+                                    int block_size, const int16_t* mv_q, uint8_t* mc);
+me_status me_compensate_planes_qpel(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur,
+                                    int width, int height, int block_size,
+                                    const int16_t* mv_q, uint8_t* out5, double* psnr);
+
 /* ---- frame-pair streaming ---- */
 
 /* Pinned (page-locked) host memory.  Frames that live in it are DMAed
@@ -387,7 +458,8 @@ me_status me_yuv_read_luma(const char* path, int width, int height, me_yuv_layou
 me_status me_yuv_write(const char* path, const uint8_t* data, size_t bytes, int append);
 
 /* MV-field file, little-endian:
- *   header (32 B): "MEMV", u16 version = 1, u16 flags (bit 0: costs present),
+ *   header (32 B): "MEMV", u16 version = 1, u16 flags (bit 0: costs present,
+ *                  bit 1: vectors are in quarter-pel units, me_mv_write_qpel),
  *                  i32 width, height, block_size, search_range, cost, u32 n_pairs
  *   per pair:      i32 ref_index, i32 cur_index,
  *                  nblocks x (i16 mvx, i16 mvy)   raster order
@@ -405,6 +477,13 @@ typedef struct me_mv_header {
 me_status me_mv_write(const char* path, int width, int height, int block_size,
                       int search_range, me_cost cost, const int* pairs, int n_pairs,
                       const int16_t* mv_xy, const uint32_t* block_cost);
+/* The same file with quarter-pel vectors (me_refine_qpel, me_full_search_qpel):
+ * flags bit 1 set, everything else as me_mv_write.  The readers accept flags
+ * 0-3 and hand them back unchanged in the header; the records are read the
+ * same way. */
+me_status me_mv_write_qpel(const char* path, int width, int height, int block_size,
+                           int search_range, me_cost cost, const int* pairs, int n_pairs,
+                           const int16_t* mv_q, const uint32_t* block_cost);
 me_status me_mv_read_header(const char* path, me_mv_header* hdr);
 /* Read everything; buffers sized from the header (pairs [n_pairs][2],
  * mv_xy [n_pairs][nblocks][2], block_cost [n_pairs][nblocks]); any may be

@@ -6,7 +6,7 @@ include/me.h); this package is the host-side mirror of the reference's
 interface over that ABI.  There is no CPU fallback.
 """
 from ._lib import (ME_COST_SAD, ME_COST_SSD, ME_COST_SSIM, ME_ECOMM, ME_EDEVICE,  # noqa: F401
-                   MEError, build)
+                   ME_QPEL_MAX_MV, MEError, build)
 from .engine import (Engine, candidate_count, num_blocks, pinned_frames,  # noqa: F401
                      last_search_path, plan_stripes, set_kernel_path, version)
 from . import io  # noqa: F401

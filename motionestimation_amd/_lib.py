@@ -24,6 +24,7 @@ ME_PATH_AUTO, ME_PATH_VALU, ME_PATH_MFMA_TILES, ME_PATH_MFMA_LEAN, ME_PATH_MFMA_
 ME_PATH_PROCESS = -1
 ME_SEARCH_PATH_SSIM, ME_SEARCH_PATH_SSIM_MFMA = 7, 8  # float-chain / matrix-core SSIM kernels
 ME_MAX_BLOCK, ME_MAX_RANGE = 64, 1024
+ME_QPEL_MAX_MV = 8000  # integer input vectors of the quarter-pel refinement
 
 # Every symbol include/me.h declares, with (restype, argtypes).
 _u8p = ctypes.c_void_p
@@ -82,6 +83,21 @@ _SIGS = {
                                     ctypes.c_int]),
     "me_mv_write": (ctypes.c_int, [ctypes.c_char_p] + [ctypes.c_int] * 5 +
                     [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "me_mv_write_qpel": (ctypes.c_int, [ctypes.c_char_p] + [ctypes.c_int] * 5 +
+                         [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "me_refine_qpel_device": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_size_t, _u8p,
+                                             ctypes.c_size_t] + [ctypes.c_int] * 6 +
+                              [ctypes.c_void_p] * 4),
+    "me_refine_qpel": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] + [ctypes.c_int] * 5 +
+                       [ctypes.c_void_p] * 3),
+    "me_full_search_qpel": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] + [ctypes.c_int] * 6 +
+                            [ctypes.c_void_p, ctypes.c_void_p]),
+    "me_motion_compensate_qpel": (ctypes.c_int, [ctypes.c_void_p, _u8p] + [ctypes.c_int] * 3 +
+                                  [ctypes.c_void_p, ctypes.c_void_p]),
+    "me_compensate_planes_qpel": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] +
+                                  [ctypes.c_int] * 3 +
+                                  [ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.POINTER(ctypes.c_double)]),
     "me_mv_read_header": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
     "me_mv_read": (ctypes.c_int, [ctypes.c_char_p] + [ctypes.c_void_p] * 4),
 }

@@ -1052,7 +1052,7 @@ me_status me_find_best_blocks(me_ctx* c, const int* ref_frame, const int* cur_fr
 
 static me_status compensate(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
                             int height, int blk, const int16_t* mv_xy, uint8_t* out,
-                            int planes, double* psnr) {
+                            int planes, double* psnr, bool qpel = false) {
   me_status s = check_args(c, ref, cur ? cur : ref, width, height, width, blk, 0, ME_COST_SSD, mv_xy);
   if (s != ME_OK) return s;
   if (!out) return fail(c, ME_EINVAL, "null output");
@@ -1072,9 +1072,9 @@ static me_status compensate(me_ctx* c, const uint8_t* ref, const uint8_t* cur, i
   HIPCHK(c, hipMemcpyAsync(d.cur, cur ? cur : ref, plane, hipMemcpyHostToDevice, d.stream));
   HIPCHK(c, hipMemcpyAsync(d.rec, mv_xy, nb * 4, hipMemcpyHostToDevice, d.stream));
   HIPCHK(c, hipMemsetAsync(d.stats, 0, 16, d.stream));
-  HIPCHK(c, me::launch_compensate(d.ref, d.cur, width, height, blk,
-                                  reinterpret_cast<int16_t*>(d.rec), d.out5, planes, d.stats,
-                                  d.stream));
+  HIPCHK(c, (qpel ? me::launch_qpel_compensate : me::launch_compensate)(
+                d.ref, d.cur, width, height, blk, reinterpret_cast<int16_t*>(d.rec), d.out5, planes,
+                d.stats, d.stream));
   unsigned long long st[2] = {0, 0};
   HIPCHK(c, hipMemcpyAsync(out, d.out5, out_bytes, hipMemcpyDeviceToHost, d.stream));
   HIPCHK(c, hipMemcpyAsync(st, d.stats, 16, hipMemcpyDeviceToHost, d.stream));
@@ -1097,6 +1097,144 @@ me_status me_compensate_planes(me_ctx* c, const uint8_t* ref, const uint8_t* cur
                                double* psnr) {
   if (!cur) return fail(c, ME_EINVAL, "null cur");
   return compensate(c, ref, cur, width, height, blk, mv_xy, out5, 1, psnr);
+}
+
+// ---- quarter-pel refinement and sub-pel compensation (me_subpel.hip) ----
+
+// The refinement's own argument rules on top of check_args.
+static me_status check_qpel(me_ctx* c, me_cost cost, const void* mv_q) {
+  if (!mv_q) return me::fail(c, ME_EINVAL, "null quarter-pel output");
+  if (cost == ME_COST_SSIM)
+    return me::fail(c, ME_EUNSUPPORTED, "quarter-pel refinement has no SSIM cost (SAD or SSD)");
+  return ME_OK;
+}
+
+// Enqueue the refinement of n_frames frames on s after the device's previous
+// search (not while capturing: me_graph_launch orders the graph).
+static me_status refine_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rfs,
+                           const uint8_t* d_cur, size_t cfs, int width, int height, int stride,
+                           int blk, me_cost cost, int n_frames, const int16_t* d_mv,
+                           int16_t* d_q, uint32_t* d_cost, hipStream_t s) {
+  if (!me::capturing(s)) {
+    me_status st = me::order_on(c, d, s);
+    if (st != ME_OK) return st;
+  }
+  const hipError_t e = me::launch_qpel_refine(d_ref, rfs, d_cur, cfs, width, height, stride, blk,
+                                              cost == ME_COST_SSD, n_frames, d_mv, d_q, d_cost, s);
+  if (e != hipSuccess)
+    return me::fail(c, ME_EDEVICE, "quarter-pel refinement launch: %s", hipGetErrorString(e));
+  return ME_OK;
+}
+
+me_status me_refine_qpel_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
+                                const uint8_t* d_cur, size_t cur_frame_stride, int width,
+                                int height, int stride, int blk, me_cost cost, int n_frames,
+                                const int16_t* d_mv_xy, int16_t* d_mv_q, uint32_t* d_block_cost,
+                                void* stream) {
+  if (!c) return ME_EINVAL;
+  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
+  me_status s = check_args(c, d_ref, d_cur, width, height, stride, blk, 0, cost, d_mv_xy);
+  if (s != ME_OK) return s;
+  if ((s = check_qpel(c, cost, d_mv_q)) != ME_OK) return s;
+  // frames must not overlap and a plane stack stays below 2 GiB, as in
+  // me_full_search_batch_device
+  const unsigned long long fb = (unsigned long long)stride * height;
+  if (n_frames > 1 && (ref_frame_stride < fb || cur_frame_stride < fb))
+    return fail(c, ME_EINVAL, "frame strides %zu / %zu below a frame's %llu bytes",
+                ref_frame_stride, cur_frame_stride, fb);
+  const unsigned long long rb = (unsigned long long)(n_frames - 1) * ref_frame_stride + fb;
+  const unsigned long long cb = (unsigned long long)(n_frames - 1) * cur_frame_stride + fb;
+  if (rb >= (1ull << 31) || cb >= (1ull << 31))
+    return fail(c, ME_EUNSUPPORTED, "batch of %llu / %llu bytes (limit 2 GiB)", rb, cb);
+  c->err[0] = 0;
+  return refine_on(c, c->devs[0], d_ref, ref_frame_stride, d_cur, cur_frame_stride, width, height,
+                   stride, blk, cost, n_frames, d_mv_xy, d_mv_q, d_block_cost,
+                   (hipStream_t)stream);
+}
+
+// Upload host planes (packed on the device) and size the record buffer:
+// d.ref, d.cur and d.rec = [mv | cost] of nb blocks, on d.stream.
+static me_status upload_pair(me_ctx* c, Dev& d, const uint8_t* ref, const uint8_t* cur, int width,
+                             int height, int stride, size_t nb) {
+  HIPCHK(c, hipSetDevice(d.id));
+  me_status s = me::own_stream(c, d);
+  if (s != ME_OK) return s;
+  const size_t plane = (size_t)width * height;
+  if ((s = grow(c, (void**)&d.ref, &d.frame_cap, 2 * plane)) != ME_OK) return s;
+  d.cur = d.ref + plane;
+  if ((s = grow(c, (void**)&d.rec, &d.rec_cap, nb * 8)) != ME_OK) return s;
+  HIPCHK(c, hipMemcpy2DAsync(d.ref, width, ref, stride, width, height, hipMemcpyHostToDevice, d.stream));
+  HIPCHK(c, hipMemcpy2DAsync(d.cur, width, cur, stride, width, height, hipMemcpyHostToDevice, d.stream));
+  return ME_OK;
+}
+
+me_status me_refine_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width, int height,
+                         int stride, int blk, me_cost cost, const int16_t* mv_xy, int16_t* mv_q,
+                         uint32_t* block_cost) {
+  me_status s = check_args(c, ref, cur, width, height, stride, blk, 0, cost, mv_xy);
+  if (s != ME_OK) return s;
+  if ((s = check_qpel(c, cost, mv_q)) != ME_OK) return s;
+  const size_t nb = (size_t)me_num_blocks(width, height, blk);
+  for (size_t i = 0; i < 2 * nb; i++)
+    if (mv_xy[i] > ME_QPEL_MAX_MV || mv_xy[i] < -ME_QPEL_MAX_MV)
+      return fail(c, ME_EINVAL, "block %zu: vector component %d beyond ME_QPEL_MAX_MV (%d)", i / 2,
+                  (int)mv_xy[i], ME_QPEL_MAX_MV);
+  c->err[0] = 0;
+  Dev& d = c->devs[0];
+  if ((s = upload_pair(c, d, ref, cur, width, height, stride, nb)) != ME_OK) return s;
+  int16_t* dmv = reinterpret_cast<int16_t*>(d.rec);
+  uint32_t* dcost = reinterpret_cast<uint32_t*>(d.rec + nb * 4);
+  HIPCHK(c, hipMemcpyAsync(dmv, mv_xy, nb * 4, hipMemcpyHostToDevice, d.stream));
+  if ((s = refine_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, cost, 1, dmv, dmv, dcost,
+                     d.stream)) != ME_OK)
+    return s;
+  HIPCHK(c, hipMemcpyAsync(mv_q, dmv, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  if (block_cost)
+    HIPCHK(c, hipMemcpyAsync(block_cost, dcost, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipStreamSynchronize(d.stream));
+  return ME_OK;
+}
+
+me_status me_full_search_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
+                              int height, int stride, int blk, int range, me_cost cost,
+                              int16_t* mv_q, uint32_t* block_cost) {
+  me_status s = check_args(c, ref, cur, width, height, stride, blk, range, cost, mv_q);
+  if (s != ME_OK) return s;
+  if ((s = check_qpel(c, cost, mv_q)) != ME_OK) return s;
+  if (c->devs.size() > 1)
+    return fail(c, ME_EUNSUPPORTED, "quarter-pel search on %zu devices (one device only)",
+                c->devs.size());
+  c->err[0] = 0;
+  Dev& d = c->devs[0];
+  const size_t nb = (size_t)me_num_blocks(width, height, blk);
+  if ((s = upload_pair(c, d, ref, cur, width, height, stride, nb)) != ME_OK) return s;
+  int16_t* dmv = reinterpret_cast<int16_t*>(d.rec);
+  uint32_t* dcost = reinterpret_cast<uint32_t*>(d.rec + nb * 4);
+  const int nby = (height + blk - 1) / blk;
+  const me::SearchJob J{d.ref, 0, d.cur, 0, 0, nby, dmv, dcost};
+  me::SearchArgs p = make_args(J, width, height, width, blk, range, cost);
+  if ((s = attach_scratch(c, d, p)) != ME_OK) return s;
+  if ((s = launch_ordered(c, d, p, &J, 1, d.stream)) != ME_OK) return s;
+  // the searched vectors stay inside the window (|m| <= ME_MAX_RANGE): refine in place
+  if ((s = refine_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, cost, 1, dmv, dmv, dcost,
+                     d.stream)) != ME_OK)
+    return s;
+  HIPCHK(c, hipMemcpyAsync(mv_q, dmv, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  if (block_cost)
+    HIPCHK(c, hipMemcpyAsync(block_cost, dcost, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  return me::device_status(c, d, d.stream);
+}
+
+me_status me_motion_compensate_qpel(me_ctx* c, const uint8_t* ref, int width, int height, int blk,
+                                    const int16_t* mv_q, uint8_t* mc) {
+  return compensate(c, ref, nullptr, width, height, blk, mv_q, mc, 0, nullptr, true);
+}
+
+me_status me_compensate_planes_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
+                                    int height, int blk, const int16_t* mv_q, uint8_t* out5,
+                                    double* psnr) {
+  if (!cur) return fail(c, ME_EINVAL, "null cur");
+  return compensate(c, ref, cur, width, height, blk, mv_q, out5, 1, psnr, true);
 }
 
 }  // extern "C"

@@ -46,7 +46,7 @@ int64_t pair_bytes(const me_mv_header& h) {
 }
 
 bool valid_header(const me_mv_header& h) {
-  if (!(memcmp(h.magic, "MEMV", 4) == 0 && h.version == 1 && h.flags <= 1 && h.width > 0 &&
+  if (!(memcmp(h.magic, "MEMV", 4) == 0 && h.version == 1 && h.flags <= 3 && h.width > 0 &&
         h.height > 0 && h.block_size > 0 && h.block_size <= ME_MAX_BLOCK &&
         h.search_range >= 0 &&
         (h.cost == ME_COST_SSD || h.cost == ME_COST_SAD || h.cost == ME_COST_SSIM)))
@@ -94,14 +94,15 @@ me_status me_yuv_write(const char* path, const uint8_t* data, size_t bytes, int 
   return fflush(f.f) == 0 ? ME_OK : ME_EIO;
 }
 
-me_status me_mv_write(const char* path, int width, int height, int block_size, int search_range,
-                      me_cost cost, const int* pairs, int n_pairs, const int16_t* mv_xy,
-                      const uint32_t* block_cost) {
+// me_mv_write / me_mv_write_qpel: `units` is the header's flags bit 1.
+static me_status write_mv(const char* path, int width, int height, int block_size,
+                          int search_range, me_cost cost, const int* pairs, int n_pairs,
+                          const int16_t* mv_xy, const uint32_t* block_cost, uint16_t units) {
   if (!path || n_pairs < 0 || (n_pairs > 0 && !mv_xy)) return ME_EINVAL;
   me_mv_header h;
   memcpy(h.magic, "MEMV", 4);
   h.version = 1;
-  h.flags = block_cost ? 1 : 0;
+  h.flags = (uint16_t)((block_cost ? 1 : 0) | units);
   h.width = width;
   h.height = height;
   h.block_size = block_size;
@@ -121,6 +122,20 @@ me_status me_mv_write(const char* path, int width, int height, int block_size, i
     if (block_cost && nb && fwrite(block_cost + nb * n, nb * 4, 1, f.f) != 1) return ME_EIO;
   }
   return fflush(f.f) == 0 ? ME_OK : ME_EIO;
+}
+
+me_status me_mv_write(const char* path, int width, int height, int block_size, int search_range,
+                      me_cost cost, const int* pairs, int n_pairs, const int16_t* mv_xy,
+                      const uint32_t* block_cost) {
+  return write_mv(path, width, height, block_size, search_range, cost, pairs, n_pairs, mv_xy,
+                  block_cost, 0);
+}
+
+me_status me_mv_write_qpel(const char* path, int width, int height, int block_size,
+                           int search_range, me_cost cost, const int* pairs, int n_pairs,
+                           const int16_t* mv_q, const uint32_t* block_cost) {
+  return write_mv(path, width, height, block_size, search_range, cost, pairs, n_pairs, mv_q,
+                  block_cost, 2);
 }
 
 static me_status read_header(FILE* f, me_mv_header* h) {

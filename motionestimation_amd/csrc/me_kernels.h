@@ -88,4 +88,17 @@ hipError_t launch_compensate(const uint8_t* ref, const uint8_t* cur, int width, 
                              int blk, const int16_t* mv, uint8_t* out5, int write_planes,
                              unsigned long long* stats, hipStream_t stream);
 
+// Quarter-pel refinement and sub-pel compensation (me_subpel.hip).
+// launch_qpel_refine: n_frames whole frames (planes at + f * frame stride,
+// records at + 2 * f * nblk / + f * nblk); mv_out may be mv_in, cost_out may
+// be null; any int16 vector reads inside the planes.  No context scratch.
+hipError_t launch_qpel_refine(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
+                              size_t cur_frame_stride, int width, int height, int stride, int blk,
+                              bool ssd, int n_frames, const int16_t* mv_in, int16_t* mv_out,
+                              uint32_t* cost_out, hipStream_t stream);
+// launch_compensate with quarter-pel vectors and edge-replicated samples.
+hipError_t launch_qpel_compensate(const uint8_t* ref, const uint8_t* cur, int width, int height,
+                                  int blk, const int16_t* mvq, uint8_t* out5, int write_planes,
+                                  unsigned long long* stats, hipStream_t stream);
+
 }  // namespace me

@@ -166,6 +166,62 @@ class Engine:
                                               _ptr(mc)), self._h)
         return mc
 
+    # ---- quarter-pel (include/me.h "quarter-pel refinement") ----
+    def refine_qpel(self, ref, cur, blk: int, mv, cost="ssd", stride=None):
+        """Refine the integer field mv [nblocks, 2] to quarter-pel.  Returns
+        (mv_q int16 [nblocks, 2], four units per pixel, cost uint32 [nblocks])."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        cur = np.ascontiguousarray(cur, dtype=np.uint8)
+        if ref.ndim != 2 or ref.shape != cur.shape:
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {ref.shape} vs {cur.shape}")
+        h, w = ref.shape
+        n = num_blocks(w, h, blk) if blk > 0 else 0
+        mv = np.ascontiguousarray(mv, np.int16)
+        if mv.size != 2 * n:
+            raise MEError(_lib.ME_EINVAL, f"mv of {mv.size // 2} records for {n} blocks")
+        q = np.zeros((max(n, 1), 2), np.int16)
+        cst = np.zeros(max(n, 1), np.uint32)
+        check(_lib.lib().me_refine_qpel(self._h, _ptr(ref), _ptr(cur), w, h, stride or w, blk,
+                                        cost_code(cost), _ptr(mv), _ptr(q), _ptr(cst)), self._h)
+        return q[:n], cst[:n]
+
+    def full_search_qpel(self, ref, cur, blk: int, span: int, cost="ssd", stride=None):
+        """full_search and refine_qpel back to back on the device.  Returns
+        (mv_q int16 [nblocks, 2] in quarter-pel units, cost uint32 [nblocks])."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        cur = np.ascontiguousarray(cur, dtype=np.uint8)
+        if ref.ndim != 2 or ref.shape != cur.shape:
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {ref.shape} vs {cur.shape}")
+        h, w = ref.shape
+        n = num_blocks(w, h, blk) if blk > 0 else 0
+        q = np.zeros((max(n, 1), 2), np.int16)
+        cst = np.zeros(max(n, 1), np.uint32)
+        check(_lib.lib().me_full_search_qpel(self._h, _ptr(ref), _ptr(cur), w, h, stride or w, blk,
+                                             span, cost_code(cost), _ptr(q), _ptr(cst)), self._h)
+        return q[:n], cst[:n]
+
+    def compensate_planes_qpel(self, ref, cur, blk: int, mv_q):
+        """compensate_planes with quarter-pel vectors (edge-replicated samples)."""
+        ref = np.ascontiguousarray(ref, np.uint8)
+        cur = np.ascontiguousarray(cur, np.uint8)
+        mv_q = np.ascontiguousarray(mv_q, np.int16)
+        h, w = ref.shape
+        out = np.zeros((5 * h, w), np.uint8)
+        psnr = ctypes.c_double()
+        check(_lib.lib().me_compensate_planes_qpel(self._h, _ptr(ref), _ptr(cur), w, h, blk,
+                                                   _ptr(mv_q), _ptr(out), ctypes.byref(psnr)),
+              self._h)
+        return out, psnr.value
+
+    def motion_compensate_qpel(self, ref, blk: int, mv_q):
+        ref = np.ascontiguousarray(ref, np.uint8)
+        mv_q = np.ascontiguousarray(mv_q, np.int16)
+        h, w = ref.shape
+        mc = np.zeros_like(ref)
+        check(_lib.lib().me_motion_compensate_qpel(self._h, _ptr(ref), w, h, blk, _ptr(mv_q),
+                                                   _ptr(mc)), self._h)
+        return mc
+
     def search_pairs(self, frames, pairs, blk: int, span: int, cost="ssd"):
         """Search many (ref, cur) frame pairs in one pipelined call.
 
@@ -276,6 +332,42 @@ class Engine:
             s = fn(*args)
             if s:
                 check(s, h)
+        return run
+
+    def refine_qpel_device(self, ref_t, cur_t, blk: int, cost, mv_t, q_t=None, cost_t=None,
+                           stream=None, width=None, height=None):
+        """Enqueue the quarter-pel refinement of resident frames
+        (me_refine_qpel_device): ref_t / cur_t are uint8 tensors (H, pitch) or a
+        batch [F, H, pitch], mv_t the integer field int16 [F * nblocks, 2], q_t
+        the result (None: in place, into mv_t), cost_t uint32/int32
+        [F * nblocks] or None.  width / height default to the tensors' last
+        two dimensions; the row pitch and the frame stride are the tensors'."""
+        self.prepared_refine_qpel(ref_t, cur_t, blk, cost, mv_t, q_t, cost_t, stream, width,
+                                  height)()
+
+    def prepared_refine_qpel(self, ref_t, cur_t, blk, cost, mv_t, q_t=None, cost_t=None,
+                             stream=None, width=None, height=None):
+        """Zero-argument callable enqueueing refine_qpel_device(...) with these buffers."""
+        if ref_t.dim() not in (2, 3) or ref_t.dim() != cur_t.dim() or \
+                (ref_t.dim() == 3 and ref_t.shape[0] != cur_t.shape[0]):
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {tuple(ref_t.shape)} / {tuple(cur_t.shape)}")
+        es = ref_t.element_size()
+        frames = ref_t.shape[0] if ref_t.dim() == 3 else 1
+        rfs = ref_t.stride(0) * es if ref_t.dim() == 3 else 0
+        cfs = cur_t.stride(0) * es if cur_t.dim() == 3 else 0
+        h = height if height else ref_t.shape[-2]
+        w = width if width else ref_t.shape[-1]
+        fn, ctx = _lib.lib().me_refine_qpel_device, self._h
+        args = (ctx, ref_t.data_ptr(), rfs, cur_t.data_ptr(), cfs, w, h, ref_t.stride(-2) * es, blk,
+                cost_code(cost), frames, mv_t.data_ptr(),
+                (q_t if q_t is not None else mv_t).data_ptr(),
+                cost_t.data_ptr() if cost_t is not None else None,
+                stream if stream is not None else _current_stream())
+
+        def run():
+            s = fn(*args)
+            if s:
+                check(s, ctx)
         return run
 
     # ---- multi-process stripes: the one exchange step in native code ----

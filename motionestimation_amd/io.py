@@ -64,11 +64,17 @@ def write_yuv(path, data: np.ndarray, append: bool = False) -> None:
     check(_lib.lib().me_yuv_write(_path(path), data.ctypes.data, data.nbytes, int(append)))
 
 
+_UNITS = {"pel": "me_mv_write", "qpel": "me_mv_write_qpel"}
+
+
 def write_mv(path, width: int, height: int, blk: int, span: int, cost, mv, block_cost=None,
-             pairs=None) -> None:
+             pairs=None, units="pel") -> None:
     """mv: [npairs, nblocks, 2] (or [nblocks, 2] for one pair) int16;
     block_cost: matching uint32 or None; pairs: [(ref, cur), ...] or None
-    (pair n = (n, n+1))."""
+    (pair n = (n, n+1)); units: "pel" (integer vectors) or "qpel" (quarter-pel
+    vectors, four units per pixel: header flags bit 1)."""
+    if units not in _UNITS:
+        raise MEError(_lib.ME_EINVAL, f"unknown mv units {units!r}")
     mv = np.ascontiguousarray(mv, np.int16)
     if mv.ndim == 2:
         mv = mv[None]
@@ -82,9 +88,10 @@ def write_mv(path, width: int, height: int, blk: int, span: int, cost, mv, block
     pr = None
     if pairs is not None:
         pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(npairs, 2))
-    check(_lib.lib().me_mv_write(_path(path), width, height, blk, span, cost_code(cost),
-                                 pr.ctypes.data if pr is not None else None, npairs,
-                                 mv.ctypes.data, cst.ctypes.data if cst is not None else None))
+    check(getattr(_lib.lib(), _UNITS[units])(_path(path), width, height, blk, span, cost_code(cost),
+                                             pr.ctypes.data if pr is not None else None, npairs,
+                                             mv.ctypes.data,
+                                             cst.ctypes.data if cst is not None else None))
 
 
 def read_mv_header(path) -> dict:
@@ -92,7 +99,8 @@ def read_mv_header(path) -> dict:
     check(_lib.lib().me_mv_read_header(_path(path), ctypes.byref(h)))
     return {"width": h.width, "height": h.height, "block_size": h.block_size,
             "search_range": h.search_range, "cost": h.cost, "n_pairs": h.n_pairs,
-            "has_cost": bool(h.flags & 1), "version": h.version}
+            "has_cost": bool(h.flags & 1), "version": h.version,
+            "units": "qpel" if h.flags & 2 else "pel"}
 
 
 def read_mv(path):
