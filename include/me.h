@@ -417,6 +417,79 @@ me_status me_compensate_planes_qpel(me_ctx* ctx, const uint8_t* ref, const uint8
                                     int width, int height, int block_size,
                                     const int16_t* mv_q, uint8_t* out5, double* psnr);
 
+/* ---- bi-predictive mode decision, joint refinement and compensation ----
+ * A current frame with two references (a past ref0 and a future ref1) and a
+ * quarter-pel field against each.  No reference counterpart; parity is against
+ * the numpy restatement tests/bipred_ref.py.  Exact integers throughout
+ * (DESIGN.md "Bi-prediction" has it in full).  P0(q) / P1(q) are the
+ * quarter-pel prediction blocks defined above, from ref0 / ref1:
+ *   - bi-prediction sample: PB(q0, q1) = (P0(q0) + P1(q1) + 1) >> 1 per pixel
+ *     (H.264 default weighting).
+ *   - costs of a block (partial edge blocks keep their true size), SAD or SSD
+ *     against the current block: c0 = cost(P0(q0)), c1 = cost(P1(q1)),
+ *     cb = cost(PB(b0, b1)), (b0, b1) starting at (q0, q1).
+ *   - joint refinement (refine != 0): two passes at quarter step, each over
+ *     the eight neighbours + (dx, dy), dx, dy in {-1, 0, 1}, in raster order
+ *     (dy outer); the centre's cost is carried over and a candidate wins only
+ *     if strictly smaller.  Pass 1 holds b0 and moves b1; pass 2 holds pass
+ *     1's b1 and moves b0.  With refine == 0, (b0, b1) = (q0, q1).
+ *   - mode: L0, L1, BI are tried in that order and a later one replaces the
+ *     best only if strictly smaller (ties go to L0, then L1); one byte per
+ *     block; block_cost is the winner's cost; cost3[nblk][3] = (c0, c1, cb).
+ *   - output vectors: (b0, b1) for mode BI, otherwise (q0, q1) unchanged.
+ *   - compensation: mc of a block is P0(v0), P1(v1) or PB(v0, v1) by its mode;
+ *     the 5 planes are [ref0, cur, mc, |ref0 - cur|, |mc - cur|], PSNR by the
+ *     rule of me_compensate_planes.
+ *   - ME_COST_SSIM, stripes and contexts with several devices are not
+ *     supported (ME_EUNSUPPORTED), for the quarter-pel refinement's reasons. */
+typedef enum me_pred_mode { ME_PRED_L0 = 0, ME_PRED_L1 = 1, ME_PRED_BI = 2 } me_pred_mode;
+#define ME_BIPRED_MAX_Q 32766 /* |component| of an input quarter-pel vector: q +- 1 fits int16 */
+
+/* n_frames >= 1 whole frames of one geometry on HBM-resident planes of ctx's
+ * first device, laid out as for me_refine_qpel_device: frame f's planes at
+ * d_ref0 + f * ref0_frame_stride, d_ref1 + f * ref1_frame_stride and d_cur +
+ * f * cur_frame_stride bytes, its records at + 2 * f * nblk (vectors), + f *
+ * nblk (d_mode, d_block_cost) and + 3 * f * nblk (d_cost3).  d_block_cost and
+ * d_cost3 may be NULL; d_mv_out0 == d_mv_q0 and d_mv_out1 == d_mv_q1 (in
+ * place) are allowed.  Asynchronous on `stream`, ordered after the context's
+ * previous search; uses no context scratch, so it can be captured without a
+ * warm-up call.  Precondition: |q| <= ME_BIPRED_MAX_Q per component (not
+ * checked: the fields are on the device); any int16 value still reads only
+ * inside the planes, its result is then unspecified. */
+me_status me_bipred_device(me_ctx* ctx, const uint8_t* d_ref0, size_t ref0_frame_stride,
+                           const uint8_t* d_ref1, size_t ref1_frame_stride, const uint8_t* d_cur,
+                           size_t cur_frame_stride, int width, int height, int stride,
+                           int block_size, me_cost cost, int refine, int n_frames,
+                           const int16_t* d_mv_q0, const int16_t* d_mv_q1, int16_t* d_mv_out0,
+                           int16_t* d_mv_out1, uint8_t* d_mode, uint32_t* d_block_cost,
+                           uint32_t* d_cost3, void* stream);
+
+/* The same on host planes of row pitch `stride`, synchronous.  ME_EINVAL for
+ * an input component beyond ME_BIPRED_MAX_Q.  block_cost and cost3 may be NULL. */
+me_status me_bipred(me_ctx* ctx, const uint8_t* ref0, const uint8_t* ref1, const uint8_t* cur,
+                    int width, int height, int stride, int block_size, me_cost cost, int refine,
+                    const int16_t* mv_q0, const int16_t* mv_q1, int16_t* mv_out0,
+                    int16_t* mv_out1, uint8_t* mode, uint32_t* block_cost, uint32_t* cost3);
+
+/* Both integer searches (ref0 and ref1 against cur), both quarter-pel
+ * refinements, then the bi-prediction with refine = 1, back to back on the
+ * device: no field visits the host.  One context device (ME_EUNSUPPORTED with
+ * several).  block_cost may be NULL. */
+me_status me_full_search_bipred(me_ctx* ctx, const uint8_t* ref0, const uint8_t* ref1,
+                                const uint8_t* cur, int width, int height, int stride,
+                                int block_size, int search_range, me_cost cost, int16_t* mv_out0,
+                                int16_t* mv_out1, uint8_t* mode, uint32_t* block_cost);
+
+/* me_motion_compensate_qpel / me_compensate_planes_qpel with two references
+ * and a mode per block (ME_EINVAL for a mode byte above ME_PRED_BI). */
+me_status me_motion_compensate_bipred(me_ctx* ctx, const uint8_t* ref0, const uint8_t* ref1,
+                                      int width, int height, int block_size, const int16_t* mv0,
+                                      const int16_t* mv1, const uint8_t* mode, uint8_t* mc);
+me_status me_compensate_planes_bipred(me_ctx* ctx, const uint8_t* ref0, const uint8_t* ref1,
+                                      const uint8_t* cur, int width, int height, int block_size,
+                                      const int16_t* mv0, const int16_t* mv1, const uint8_t* mode,
+                                      uint8_t* out5, double* psnr);
+
 /* ---- frame-pair streaming ---- */
 
 /* Pinned (page-locked) host memory.  Frames that live in it are DMAed

@@ -6,7 +6,8 @@ include/me.h); this package is the host-side mirror of the reference's
 interface over that ABI.  There is no CPU fallback.
 """
 from ._lib import (ME_COST_SAD, ME_COST_SSD, ME_COST_SSIM, ME_ECOMM, ME_EDEVICE,  # noqa: F401
-                   ME_QPEL_MAX_MV, MEError, build)
+                   ME_BIPRED_MAX_Q, ME_PRED_BI, ME_PRED_L0, ME_PRED_L1, ME_QPEL_MAX_MV, MEError,
+                   build)
 from .engine import (Engine, candidate_count, num_blocks, pinned_frames,  # noqa: F401
                      last_search_path, plan_stripes, set_kernel_path, version)
 from . import io  # noqa: F401

@@ -25,6 +25,8 @@ ME_PATH_PROCESS = -1
 ME_SEARCH_PATH_SSIM, ME_SEARCH_PATH_SSIM_MFMA = 7, 8  # float-chain / matrix-core SSIM kernels
 ME_MAX_BLOCK, ME_MAX_RANGE = 64, 1024
 ME_QPEL_MAX_MV = 8000  # integer input vectors of the quarter-pel refinement
+ME_PRED_L0, ME_PRED_L1, ME_PRED_BI = 0, 1, 2  # me_pred_mode
+ME_BIPRED_MAX_Q = 32766  # input quarter-pel vectors of the bi-prediction
 
 # Every symbol include/me.h declares, with (restype, argtypes).
 _u8p = ctypes.c_void_p
@@ -98,6 +100,18 @@ _SIGS = {
                                   [ctypes.c_int] * 3 +
                                   [ctypes.c_void_p, ctypes.c_void_p,
                                    ctypes.POINTER(ctypes.c_double)]),
+    "me_bipred_device": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_size_t, _u8p,
+                                        ctypes.c_size_t, _u8p, ctypes.c_size_t] +
+                         [ctypes.c_int] * 7 + [ctypes.c_void_p] * 8),
+    "me_bipred": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, _u8p] + [ctypes.c_int] * 6 +
+                  [ctypes.c_void_p] * 7),
+    "me_full_search_bipred": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, _u8p] +
+                              [ctypes.c_int] * 6 + [ctypes.c_void_p] * 4),
+    "me_motion_compensate_bipred": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] +
+                                    [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4),
+    "me_compensate_planes_bipred": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, _u8p] +
+                                    [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4 +
+                                    [ctypes.POINTER(ctypes.c_double)]),
     "me_mv_read_header": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
     "me_mv_read": (ctypes.c_int, [ctypes.c_char_p] + [ctypes.c_void_p] * 4),
 }

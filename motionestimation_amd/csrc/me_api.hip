@@ -1237,4 +1237,224 @@ me_status me_compensate_planes_qpel(me_ctx* c, const uint8_t* ref, const uint8_t
   return compensate(c, ref, cur, width, height, blk, mv_q, out5, 1, psnr, true);
 }
 
+// ---- bi-prediction (me_subpel.hip) ----
+
+static me_status check_bipred(me_ctx* c, me_cost cost, const void* ref1, const void* q1,
+                              const void* out0, const void* out1, const void* mode) {
+  if (!ref1 || !q1 || !out0 || !out1 || !mode)
+    return me::fail(c, ME_EINVAL, "null bi-prediction plane, field or mode pointer");
+  if (cost == ME_COST_SSIM)
+    return me::fail(c, ME_EUNSUPPORTED, "bi-prediction has no SSIM cost (SAD or SSD)");
+  return ME_OK;
+}
+
+// Enqueue the bi-prediction of n_frames frames on s after the device's
+// previous search (not while capturing: me_graph_launch orders the graph).
+static me_status bipred_on(me_ctx* c, Dev& d, const uint8_t* d_ref0, size_t r0fs,
+                           const uint8_t* d_ref1, size_t r1fs, const uint8_t* d_cur, size_t cfs,
+                           int width, int height, int stride, int blk, me_cost cost, int refine,
+                           int n_frames, const int16_t* q0, const int16_t* q1, int16_t* out0,
+                           int16_t* out1, uint8_t* mode, uint32_t* d_cost, uint32_t* d_cost3,
+                           hipStream_t s) {
+  if (!me::capturing(s)) {
+    me_status st = me::order_on(c, d, s);
+    if (st != ME_OK) return st;
+  }
+  const hipError_t e = me::launch_bipred(d_ref0, r0fs, d_ref1, r1fs, d_cur, cfs, width, height,
+                                         stride, blk, cost == ME_COST_SSD, refine, n_frames, q0, q1,
+                                         out0, out1, mode, d_cost, d_cost3, s);
+  if (e != hipSuccess)
+    return me::fail(c, ME_EDEVICE, "bi-prediction launch: %s", hipGetErrorString(e));
+  return ME_OK;
+}
+
+me_status me_bipred_device(me_ctx* c, const uint8_t* d_ref0, size_t ref0_frame_stride,
+                           const uint8_t* d_ref1, size_t ref1_frame_stride, const uint8_t* d_cur,
+                           size_t cur_frame_stride, int width, int height, int stride, int blk,
+                           me_cost cost, int refine, int n_frames, const int16_t* d_mv_q0,
+                           const int16_t* d_mv_q1, int16_t* d_mv_out0, int16_t* d_mv_out1,
+                           uint8_t* d_mode, uint32_t* d_block_cost, uint32_t* d_cost3,
+                           void* stream) {
+  if (!c) return ME_EINVAL;
+  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
+  me_status s = check_args(c, d_ref0, d_cur, width, height, stride, blk, 0, cost, d_mv_q0);
+  if (s != ME_OK) return s;
+  if ((s = check_bipred(c, cost, d_ref1, d_mv_q1, d_mv_out0, d_mv_out1, d_mode)) != ME_OK) return s;
+  // frames must not overlap and a plane stack stays below 2 GiB, as in
+  // me_refine_qpel_device
+  const unsigned long long fb = (unsigned long long)stride * height;
+  const size_t fs[3] = {ref0_frame_stride, ref1_frame_stride, cur_frame_stride};
+  for (size_t v : fs) {
+    if (n_frames > 1 && v < fb)
+      return fail(c, ME_EINVAL, "frame stride %zu below a frame's %llu bytes", v, fb);
+    const unsigned long long bytes = (unsigned long long)(n_frames - 1) * v + fb;
+    if (bytes >= (1ull << 31))
+      return fail(c, ME_EUNSUPPORTED, "batch of %llu bytes (limit 2 GiB)", bytes);
+  }
+  c->err[0] = 0;
+  return bipred_on(c, c->devs[0], d_ref0, ref0_frame_stride, d_ref1, ref1_frame_stride, d_cur,
+                   cur_frame_stride, width, height, stride, blk, cost, refine, n_frames, d_mv_q0,
+                   d_mv_q1, d_mv_out0, d_mv_out1, d_mode, d_block_cost, d_cost3,
+                   (hipStream_t)stream);
+}
+
+// Device buffers of the host bi-prediction calls on d.stream: three packed
+// planes (d.ref = ref0, d.cur, then ref1) and the records of nb blocks in
+// d.rec.
+struct BipredBufs {
+  uint8_t* ref1;
+  int16_t *q0, *q1;
+  uint32_t *cost, *cost3;
+  uint8_t* mode;
+};
+static me_status upload_triple(me_ctx* c, Dev& d, const uint8_t* ref0, const uint8_t* ref1,
+                               const uint8_t* cur, int width, int height, int stride, size_t nb,
+                               BipredBufs* B) {
+  HIPCHK(c, hipSetDevice(d.id));
+  me_status s = me::own_stream(c, d);
+  if (s != ME_OK) return s;
+  const size_t plane = (size_t)width * height;
+  if ((s = grow(c, (void**)&d.ref, &d.frame_cap, 3 * plane)) != ME_OK) return s;
+  d.cur = d.ref + plane;
+  B->ref1 = d.ref + 2 * plane;
+  // q0 | q1 | cost | cost3 | mode: 4 + 4 + 4 + 12 + 1 bytes per block
+  if ((s = grow(c, (void**)&d.rec, &d.rec_cap, nb * 28)) != ME_OK) return s;
+  B->q0 = reinterpret_cast<int16_t*>(d.rec);
+  B->q1 = reinterpret_cast<int16_t*>(d.rec + nb * 4);
+  B->cost = reinterpret_cast<uint32_t*>(d.rec + nb * 8);
+  B->cost3 = reinterpret_cast<uint32_t*>(d.rec + nb * 12);
+  B->mode = reinterpret_cast<uint8_t*>(d.rec + nb * 24);
+  HIPCHK(c, hipMemcpy2DAsync(d.ref, width, ref0, stride, width, height, hipMemcpyHostToDevice, d.stream));
+  HIPCHK(c, hipMemcpy2DAsync(d.cur, width, cur, stride, width, height, hipMemcpyHostToDevice, d.stream));
+  HIPCHK(c, hipMemcpy2DAsync(B->ref1, width, ref1, stride, width, height, hipMemcpyHostToDevice, d.stream));
+  return ME_OK;
+}
+
+me_status me_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* ref1, const uint8_t* cur,
+                    int width, int height, int stride, int blk, me_cost cost, int refine,
+                    const int16_t* mv_q0, const int16_t* mv_q1, int16_t* mv_out0,
+                    int16_t* mv_out1, uint8_t* mode, uint32_t* block_cost, uint32_t* cost3) {
+  me_status s = check_args(c, ref0, cur, width, height, stride, blk, 0, cost, mv_q0);
+  if (s != ME_OK) return s;
+  if ((s = check_bipred(c, cost, ref1, mv_q1, mv_out0, mv_out1, mode)) != ME_OK) return s;
+  const size_t nb = (size_t)me_num_blocks(width, height, blk);
+  for (size_t i = 0; i < 2 * nb; i++)
+    for (const int16_t* q : {mv_q0, mv_q1})
+      if (q[i] > ME_BIPRED_MAX_Q || q[i] < -ME_BIPRED_MAX_Q)
+        return fail(c, ME_EINVAL, "block %zu: vector component %d beyond ME_BIPRED_MAX_Q (%d)",
+                    i / 2, (int)q[i], ME_BIPRED_MAX_Q);
+  c->err[0] = 0;
+  Dev& d = c->devs[0];
+  BipredBufs B;
+  if ((s = upload_triple(c, d, ref0, ref1, cur, width, height, stride, nb, &B)) != ME_OK) return s;
+  HIPCHK(c, hipMemcpyAsync(B.q0, mv_q0, nb * 4, hipMemcpyHostToDevice, d.stream));
+  HIPCHK(c, hipMemcpyAsync(B.q1, mv_q1, nb * 4, hipMemcpyHostToDevice, d.stream));
+  if ((s = bipred_on(c, d, d.ref, 0, B.ref1, 0, d.cur, 0, width, height, width, blk, cost, refine,
+                     1, B.q0, B.q1, B.q0, B.q1, B.mode, B.cost, B.cost3, d.stream)) != ME_OK)
+    return s;
+  HIPCHK(c, hipMemcpyAsync(mv_out0, B.q0, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipMemcpyAsync(mv_out1, B.q1, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipMemcpyAsync(mode, B.mode, nb, hipMemcpyDeviceToHost, d.stream));
+  if (block_cost)
+    HIPCHK(c, hipMemcpyAsync(block_cost, B.cost, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  if (cost3) HIPCHK(c, hipMemcpyAsync(cost3, B.cost3, nb * 12, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipStreamSynchronize(d.stream));
+  return ME_OK;
+}
+
+me_status me_full_search_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* ref1,
+                                const uint8_t* cur, int width, int height, int stride, int blk,
+                                int range, me_cost cost, int16_t* mv_out0, int16_t* mv_out1,
+                                uint8_t* mode, uint32_t* block_cost) {
+  me_status s = check_args(c, ref0, cur, width, height, stride, blk, range, cost, mv_out0);
+  if (s != ME_OK) return s;
+  if ((s = check_bipred(c, cost, ref1, mv_out1, mv_out0, mv_out1, mode)) != ME_OK) return s;
+  if (c->devs.size() > 1)
+    return fail(c, ME_EUNSUPPORTED, "bi-predictive search on %zu devices (one device only)",
+                c->devs.size());
+  c->err[0] = 0;
+  Dev& d = c->devs[0];
+  const size_t nb = (size_t)me_num_blocks(width, height, blk);
+  BipredBufs B;
+  if ((s = upload_triple(c, d, ref0, ref1, cur, width, height, stride, nb, &B)) != ME_OK) return s;
+  const int nby = (height + blk - 1) / blk;
+  // search and refine against ref0, then ref1 (B.cost is overwritten by each
+  // stage; the bi-prediction's is the one that is read back)
+  const uint8_t* refs[2] = {d.ref, B.ref1};
+  int16_t* fields[2] = {B.q0, B.q1};
+  for (int k = 0; k < 2; k++) {
+    const me::SearchJob J{refs[k], 0, d.cur, 0, 0, nby, fields[k], B.cost};
+    me::SearchArgs p = make_args(J, width, height, width, blk, range, cost);
+    if ((s = attach_scratch(c, d, p)) != ME_OK) return s;
+    if ((s = launch_ordered(c, d, p, &J, 1, d.stream)) != ME_OK) return s;
+    // the searched vectors stay inside the window (|m| <= ME_MAX_RANGE): refine in place
+    if ((s = refine_on(c, d, refs[k], 0, d.cur, 0, width, height, width, blk, cost, 1, fields[k],
+                       fields[k], B.cost, d.stream)) != ME_OK)
+      return s;
+  }
+  if ((s = bipred_on(c, d, d.ref, 0, B.ref1, 0, d.cur, 0, width, height, width, blk, cost, 1, 1,
+                     B.q0, B.q1, B.q0, B.q1, B.mode, B.cost, nullptr, d.stream)) != ME_OK)
+    return s;
+  HIPCHK(c, hipMemcpyAsync(mv_out0, B.q0, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipMemcpyAsync(mv_out1, B.q1, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipMemcpyAsync(mode, B.mode, nb, hipMemcpyDeviceToHost, d.stream));
+  if (block_cost)
+    HIPCHK(c, hipMemcpyAsync(block_cost, B.cost, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  return me::device_status(c, d, d.stream);
+}
+
+static me_status compensate_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* ref1,
+                                   const uint8_t* cur, int width, int height, int blk,
+                                   const int16_t* mv0, const int16_t* mv1, const uint8_t* mode,
+                                   uint8_t* out, int planes, double* psnr) {
+  me_status s = check_args(c, ref0, cur ? cur : ref0, width, height, width, blk, 0, ME_COST_SSD, mv0);
+  if (s != ME_OK) return s;
+  if (!ref1 || !mv1 || !mode || !out)
+    return fail(c, ME_EINVAL, "null bi-prediction plane, field, mode or output pointer");
+  const size_t nb = (size_t)me_num_blocks(width, height, blk);
+  for (size_t i = 0; i < nb; i++)
+    if (mode[i] > ME_PRED_BI)
+      return fail(c, ME_EINVAL, "block %zu: mode %d (0, 1 or 2)", i, (int)mode[i]);
+  Dev& d = c->devs[0];
+  BipredBufs B;
+  if ((s = upload_triple(c, d, ref0, ref1, cur ? cur : ref0, width, height, width, nb, &B)) != ME_OK)
+    return s;
+  const size_t plane = (size_t)width * height;
+  size_t scap = d.stats ? 16 : 0;
+  if ((s = grow(c, (void**)&d.stats, &scap, 16)) != ME_OK) return s;
+  const size_t out_bytes = planes ? 5 * plane : plane;
+  if ((s = grow(c, (void**)&d.out5, &d.out_cap, out_bytes)) != ME_OK) return s;
+  HIPCHK(c, hipMemcpyAsync(B.q0, mv0, nb * 4, hipMemcpyHostToDevice, d.stream));
+  HIPCHK(c, hipMemcpyAsync(B.q1, mv1, nb * 4, hipMemcpyHostToDevice, d.stream));
+  HIPCHK(c, hipMemcpyAsync(B.mode, mode, nb, hipMemcpyHostToDevice, d.stream));
+  HIPCHK(c, hipMemsetAsync(d.stats, 0, 16, d.stream));
+  HIPCHK(c, me::launch_bipred_compensate(d.ref, B.ref1, d.cur, width, height, blk, B.q0, B.q1,
+                                         B.mode, d.out5, planes, d.stats, d.stream));
+  unsigned long long st[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(out, d.out5, out_bytes, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipMemcpyAsync(st, d.stats, 16, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipStreamSynchronize(d.stream));
+  if (psnr) {  // as compensate()
+    double mse = (double)st[0];
+    mse /= (double)width * height;
+    *psnr = mse == 0 ? 99.0 : 20 * log10((double)st[1]) - 10 * log10(mse);
+  }
+  return ME_OK;
+}
+
+me_status me_motion_compensate_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* ref1,
+                                      int width, int height, int blk, const int16_t* mv0,
+                                      const int16_t* mv1, const uint8_t* mode, uint8_t* mc) {
+  return compensate_bipred(c, ref0, ref1, nullptr, width, height, blk, mv0, mv1, mode, mc, 0,
+                           nullptr);
+}
+
+me_status me_compensate_planes_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* ref1,
+                                      const uint8_t* cur, int width, int height, int blk,
+                                      const int16_t* mv0, const int16_t* mv1, const uint8_t* mode,
+                                      uint8_t* out5, double* psnr) {
+  if (!cur) return fail(c, ME_EINVAL, "null cur");
+  return compensate_bipred(c, ref0, ref1, cur, width, height, blk, mv0, mv1, mode, out5, 1, psnr);
+}
+
 }  // extern "C"

@@ -101,4 +101,23 @@ hipError_t launch_qpel_compensate(const uint8_t* ref, const uint8_t* cur, int wi
                                   int blk, const int16_t* mvq, uint8_t* out5, int write_planes,
                                   unsigned long long* stats, hipStream_t stream);
 
+// Bi-prediction (me_subpel.hip): per block the costs of ref0 at q0, ref1 at q1
+// and their rounded average, the joint quarter-step refinement of the pair
+// (refine != 0) and the mode.  Frames and records laid out as for
+// launch_qpel_refine; mode_out one byte per block, cost3_out [3] per block;
+// the outputs may be the inputs, cost_out / cost3_out may be null.  No context
+// scratch; any int16 vector reads inside the planes.
+hipError_t launch_bipred(const uint8_t* ref0, size_t ref0_frame_stride, const uint8_t* ref1,
+                         size_t ref1_frame_stride, const uint8_t* cur, size_t cur_frame_stride,
+                         int width, int height, int stride, int blk, bool ssd, int refine,
+                         int n_frames, const int16_t* q0_in, const int16_t* q1_in, int16_t* q0_out,
+                         int16_t* q1_out, uint8_t* mode_out, uint32_t* cost_out,
+                         uint32_t* cost3_out, hipStream_t stream);
+// launch_qpel_compensate with two references and a mode byte (0, 1, 2) per block.
+hipError_t launch_bipred_compensate(const uint8_t* ref0, const uint8_t* ref1, const uint8_t* cur,
+                                    int width, int height, int blk, const int16_t* mv0,
+                                    const int16_t* mv1, const uint8_t* mode, uint8_t* out5,
+                                    int write_planes, unsigned long long* stats,
+                                    hipStream_t stream);
+
 }  // namespace me

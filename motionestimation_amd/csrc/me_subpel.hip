@@ -1,7 +1,8 @@
-// me_subpel.hip -- quarter-pel refinement of an integer MV field and sub-pel
-// motion compensation (include/me.h "quarter-pel"; DESIGN.md has the
-// definition and the LDS layout).  No reference counterpart: the reference
-// stops at integer vectors.
+// me_subpel.hip -- quarter-pel refinement of an integer MV field, sub-pel
+// motion compensation, and the bi-predictive mode decision over two
+// quarter-pel fields with its compensation (include/me.h "quarter-pel" and
+// "bi-predictive"; DESIGN.md has the definitions and the LDS layouts).  No
+// reference counterpart: the reference stops at integer vectors.
 //
 // Sample definition (H.264 luma, exact integers): reference samples are edge
 // replicated, half samples are the 6-tap (1,-5,20,20,-5,1) filter rounded
@@ -28,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "me.h"
 #include "me_kernels.h"
 
 namespace me {
@@ -81,12 +83,13 @@ __device__ __forceinline__ int tap6(int a, int b, int c, int d, int e, int f) {
 }
 
 // r -> b1 -> hg (barriers inside: every thread of the block calls it, after
-// qpel_stage; hg is complete on return).
+// qpel_stage; hg is complete on return).  hg is s.hg, or a second grid of the
+// same layout (the bi-prediction kernel keeps one per reference).
 template <int TB>
-__device__ __forceinline__ void qpel_half_grid(QpelLds<TB>& s, int bw, int bh) {
+__device__ __forceinline__ void qpel_half_grid(QpelLds<TB>& s, uint8_t* hg, int bw, int bh) {
   using G = QpelGeom<TB>;
-  uint8_t* const he = s.hg;             // even X: column X / 2
-  uint8_t* const ho = s.hg + G::PLANE;  // odd X: column (X - 1) / 2
+  uint8_t* const he = hg;             // even X: column X / 2
+  uint8_t* const ho = hg + G::PLANE;  // odd X: column (X - 1) / 2
   __syncthreads();
   // b1 column c is the half sample between pixels bx-1+c and bx+c
   for (int i = threadIdx.x; i < G::RW * G::BW; i += G::NT) {
@@ -128,6 +131,10 @@ __device__ __forceinline__ void qpel_half_grid(QpelLds<TB>& s, int bw, int bh) {
   }
   __syncthreads();
 }
+template <int TB>
+__device__ __forceinline__ void qpel_half_grid(QpelLds<TB>& s, int bw, int bh) {
+  qpel_half_grid<TB>(s, s.hg, bw, bh);
+}
 
 // The two half-grid samples whose rounded average is the prediction sample at
 // quarter offset (ox, oy), |ox|, |oy| <= 3, from the block's integer position,
@@ -152,24 +159,33 @@ __device__ __forceinline__ QpelTaps qpel_taps(int ox, int oy) {
 // hg samples at half-pel offset (tx, ty), tx in [-2, 2], of the 4 pixels
 // (px0 .. px0 + 3, py) of the block, px0 a multiple of 4: bytes 0..3.
 template <int TB>
-__device__ __forceinline__ uint32_t qpel_load4(const QpelLds<TB>& s, int px0, int py, int tx,
+__device__ __forceinline__ uint32_t qpel_load4(const uint8_t* hg, int px0, int py, int tx,
                                                int ty) {
   using G = QpelGeom<TB>;
   // sample X = 2 px + 2 + tx: plane tx & 1, column px + 1 + (tx >> 1)
   const int at = (tx & 1) * G::PLANE + (2 * py + 2 + ty) * G::EP + px0;
-  const uint32_t lo = *reinterpret_cast<const uint32_t*>(&s.hg[at]);
-  const uint32_t hi = *reinterpret_cast<const uint32_t*>(&s.hg[at + 4]);
+  const uint32_t lo = *reinterpret_cast<const uint32_t*>(&hg[at]);
+  const uint32_t hi = *reinterpret_cast<const uint32_t*>(&hg[at + 4]);
   return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(1 + (tx >> 1)));
 }
 
-// Prediction samples of 4 adjacent pixels: per byte (a + b + 1) >> 1.
+// Per byte (a + b + 1) >> 1.
+__device__ __forceinline__ uint32_t avg4(uint32_t a, uint32_t b) {
+  return (a | b) - (((a ^ b) >> 1) & 0x7F7F7F7Fu);
+}
+
+// Prediction samples of 4 adjacent pixels from the half grid hg.
+template <int TB>
+__device__ __forceinline__ uint32_t qpel_pred4(const uint8_t* hg, int px0, int py,
+                                               const QpelTaps& t) {
+  const uint32_t a = qpel_load4<TB>(hg, px0, py, t.tx0, t.ty0);
+  if (t.tx0 == t.tx1 && t.ty0 == t.ty1) return a;  // uniform over the block
+  return avg4(a, qpel_load4<TB>(hg, px0, py, t.tx1, t.ty1));
+}
 template <int TB>
 __device__ __forceinline__ uint32_t qpel_pred4(const QpelLds<TB>& s, int px0, int py,
                                                const QpelTaps& t) {
-  const uint32_t a = qpel_load4<TB>(s, px0, py, t.tx0, t.ty0);
-  if (t.tx0 == t.tx1 && t.ty0 == t.ty1) return a;  // uniform over the block
-  const uint32_t b = qpel_load4<TB>(s, px0, py, t.tx1, t.ty1);
-  return (a | b) - (((a ^ b) >> 1) & 0x7F7F7F7Fu);
+  return qpel_pred4<TB>(s.hg, px0, py, t);
 }
 
 // Sum over the wave, the same (scalar) value in every lane.
@@ -379,6 +395,249 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_qpel_compensate_kernel(
   }
 }
 
+// ---- bi-prediction (include/me.h "bi-prediction"; DESIGN.md "Bi-prediction") ----
+//
+// The window r and the intermediates b1 are staged for ref0 and turned into
+// the half grid hg (of QpelLds), then reused for ref1 -> hg1: only the half
+// grid is doubled.  Each window sits at its vector's nearest integer position
+// (q + 2) >> 2, so the vector's own quarter offset is in [-2, 1] and its eight
+// quarter-step neighbours are in [-3, 2]: inside the +-3 the half grid covers.
+template <int TB>
+struct BipredLds : QpelLds<TB> {
+  alignas(4) uint8_t hg1[2 * QpelGeom<TB>::PLANE];
+};
+
+// Adds the cost terms of 4 (masked) prediction bytes p against cur bytes c.
+template <bool SSD>
+__device__ __forceinline__ void cost4(uint32_t p, uint32_t c, uint32_t& pp, uint32_t& pc) {
+  if (SSD) {
+    pp = __builtin_amdgcn_udot4(p, p, pp, false);
+    pc = __builtin_amdgcn_udot4(p, c, pc, false);
+  } else {
+    pp = __builtin_amdgcn_sad_u8(p, c, pp);
+  }
+}
+
+// v[0..N) summed over the block, N <= 9: every thread returns the same numbers.
+template <int TB, int N>
+__device__ __forceinline__ void block_sums(QpelLds<TB>& s, uint32_t (&v)[N]) {
+  using G = QpelGeom<TB>;
+#pragma unroll
+  for (int n = 0; n < N; n++) v[n] = wave_sum(v[n]);
+  if (G::NW > 1) {
+    __syncthreads();  // the previous sums have been read
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+      for (int n = 0; n < N; n++) s.red[(threadIdx.x >> 6) * 9 + n] = v[n];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < N; n++) {
+      v[n] = 0;
+      for (int w = 0; w < G::NW; w++) v[n] += s.red[w * 9 + n];
+    }
+  }
+}
+
+// One pass of the joint refinement: the eight quarter-step neighbours of
+// (cx, cy) on the half grid hg, each averaged with the other reference's
+// prediction held in registers, in raster order; a candidate replaces
+// (best, bx, by) only with a strictly smaller cost.
+template <int TB, bool SSD>
+__device__ __forceinline__ void bipred_pass(QpelLds<TB>& s, const QpelPix<TB>& P, uint32_t cc,
+                                            const uint32_t (&held)[QpelGeom<TB>::GPL],
+                                            const uint8_t* hg, int cx, int cy, uint32_t& best,
+                                            int& bx, int& by) {
+  using G = QpelGeom<TB>;
+  uint32_t v[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const int n = j < 4 ? j : j + 1;  // raster index without the centre
+    const QpelTaps t = qpel_taps(cx + n % 3 - 1, cy + n / 3 - 1);
+    uint32_t pp = 0, pc = 0;
+#pragma unroll
+    for (int k = 0; k < G::GPL; k++) {
+      const uint32_t p = avg4(held[k], qpel_pred4<TB>(hg, P.px0[k], P.py[k], t)) & P.mask[k];
+      cost4<SSD>(p, P.cur[k], pp, pc);
+    }
+    v[j] = SSD ? pp + cc - 2 * pc : pp;
+  }
+  block_sums<TB, 8>(s, v);
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const int n = j < 4 ? j : j + 1;
+    if (v[j] < best) {
+      best = v[j];
+      bx = cx + n % 3 - 1;
+      by = cy + n / 3 - 1;
+    }
+  }
+}
+
+// One block (workgroup) per macroblock, the frame in blockIdx.y.  The outputs
+// may be the inputs: a block reads its own records before its first barrier
+// and writes them after its last.
+template <int TB, bool SSD>
+__global__ __launch_bounds__(QpelGeom<TB>::NT) void me_bipred_kernel(
+    const uint8_t* __restrict__ ref0, size_t ref0_frame_stride, const uint8_t* __restrict__ ref1,
+    size_t ref1_frame_stride, const uint8_t* __restrict__ cur, size_t cur_frame_stride, int width,
+    int height, int stride, int blk, int nbx, int nblk, int refine, const int16_t* q0_in,
+    const int16_t* q1_in, int16_t* q0_out, int16_t* q1_out, uint8_t* mode_out, uint32_t* cost_out,
+    uint32_t* cost3_out) {
+  using G = QpelGeom<TB>;
+  __shared__ BipredLds<TB> s;
+  const int b = blockIdx.x, f = blockIdx.y;
+  const size_t rec = (size_t)f * nblk + b;
+  const int x0 = (b % nbx) * blk, y0 = (b / nbx) * blk;
+  const int bw = min(blk, width - x0), bh = min(blk, height - y0);
+  const int q0x = q0_in[2 * rec], q0y = q0_in[2 * rec + 1];
+  const int q1x = q1_in[2 * rec], q1y = q1_in[2 * rec + 1];
+  // integer window positions and the vectors' quarter offsets from them
+  const int i0x = (q0x + 2) >> 2, i0y = (q0y + 2) >> 2;
+  const int i1x = (q1x + 2) >> 2, i1y = (q1y + 2) >> 2;
+  ref0 += (size_t)f * ref0_frame_stride;
+  ref1 += (size_t)f * ref1_frame_stride;
+  cur += (size_t)f * cur_frame_stride;
+
+  QpelPix<TB> P;
+  qpel_pixels<TB>(P, cur + (size_t)y0 * stride + x0, stride, bw, bh);
+  uint32_t cc = 0;
+  if (SSD) {
+#pragma unroll
+    for (int k = 0; k < G::GPL; k++) cc = __builtin_amdgcn_udot4(P.cur[k], P.cur[k], cc, false);
+  }
+  qpel_stage<TB>(s, ref0, width, height, stride, x0 + i0x, y0 + i0y, bw, bh);
+  qpel_half_grid<TB>(s, s.hg, bw, bh);
+  // hg is complete and r / b1 are free again (qpel_half_grid ends on a barrier)
+  qpel_stage<TB>(s, ref1, width, height, stride, x0 + i1x, y0 + i1y, bw, bh);
+  qpel_half_grid<TB>(s, s.hg1, bw, bh);
+
+  int o0x = q0x - 4 * i0x, o0y = q0y - 4 * i0y;  // b0 - 4 * i0, in [-2, 1]
+  int o1x = q1x - 4 * i1x, o1y = q1y - 4 * i1y;
+  uint32_t held[G::GPL];  // the prediction that stays while the other one moves
+  uint32_t c3[3];
+  {
+    const QpelTaps t0 = qpel_taps(o0x, o0y), t1 = qpel_taps(o1x, o1y);
+    uint32_t pp[3] = {0, 0, 0}, pc[3] = {0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < G::GPL; k++) {
+      const uint32_t a = qpel_pred4<TB>(s.hg, P.px0[k], P.py[k], t0);
+      const uint32_t c = qpel_pred4<TB>(s.hg1, P.px0[k], P.py[k], t1);
+      held[k] = a;
+      cost4<SSD>(a & P.mask[k], P.cur[k], pp[0], pc[0]);
+      cost4<SSD>(c & P.mask[k], P.cur[k], pp[1], pc[1]);
+      cost4<SSD>(avg4(a, c) & P.mask[k], P.cur[k], pp[2], pc[2]);
+    }
+#pragma unroll
+    for (int n = 0; n < 3; n++) c3[n] = SSD ? pp[n] + cc - 2 * pc[n] : pp[n];
+    block_sums<TB, 3>(s, c3);
+  }
+  if (refine) {  // uniform over the grid
+    bipred_pass<TB, SSD>(s, P, cc, held, s.hg1, o1x, o1y, c3[2], o1x, o1y);
+    const QpelTaps t1 = qpel_taps(o1x, o1y);
+#pragma unroll
+    for (int k = 0; k < G::GPL; k++) held[k] = qpel_pred4<TB>(s.hg1, P.px0[k], P.py[k], t1);
+    bipred_pass<TB, SSD>(s, P, cc, held, s.hg, o0x, o0y, c3[2], o0x, o0y);
+  }
+  if (threadIdx.x == 0) {
+    // L0, L1, BI in that order, a later mode only with a strictly smaller cost
+    uint32_t best = c3[0];
+    int mode = ME_PRED_L0;
+    if (c3[1] < best) best = c3[1], mode = ME_PRED_L1;
+    if (c3[2] < best) best = c3[2], mode = ME_PRED_BI;
+    const bool bi = mode == ME_PRED_BI;
+    q0_out[2 * rec] = (int16_t)(bi ? 4 * i0x + o0x : q0x);
+    q0_out[2 * rec + 1] = (int16_t)(bi ? 4 * i0y + o0y : q0y);
+    q1_out[2 * rec] = (int16_t)(bi ? 4 * i1x + o1x : q1x);
+    q1_out[2 * rec + 1] = (int16_t)(bi ? 4 * i1y + o1y : q1y);
+    mode_out[rec] = (uint8_t)mode;
+    if (cost_out) cost_out[rec] = best;
+    if (cost3_out) {
+      cost3_out[3 * rec] = c3[0];
+      cost3_out[3 * rec + 1] = c3[1];
+      cost3_out[3 * rec + 2] = c3[2];
+    }
+  }
+}
+
+// me_qpel_compensate_kernel with a mode per block: the block is P0(v0), P1(v1)
+// or their rounded average.  One half grid: a reference's samples are in
+// registers before the next one is staged.  Plane 0 and |ref - cur| are ref0's.
+template <int TB>
+__global__ __launch_bounds__(QpelGeom<TB>::NT) void me_bipred_compensate_kernel(
+    const uint8_t* __restrict__ ref0, const uint8_t* __restrict__ ref1,
+    const uint8_t* __restrict__ cur, int width, int height, int blk, int nbx,
+    const int16_t* __restrict__ mv0, const int16_t* __restrict__ mv1,
+    const uint8_t* __restrict__ mode, uint8_t* __restrict__ out5, int write_planes,
+    unsigned long long* stats) {
+  using G = QpelGeom<TB>;
+  __shared__ QpelLds<TB> s;
+  const int b = blockIdx.x;
+  const int x0 = (b % nbx) * blk, y0 = (b / nbx) * blk;
+  const int bw = min(blk, width - x0), bh = min(blk, height - y0);
+  const int md = mode[b];  // uniform over the block (the host rejects md > 2)
+  QpelPix<TB> P;
+  qpel_pixels<TB>(P, nullptr, 0, bw, bh);
+  uint32_t p4[G::GPL] = {};
+  if (md != ME_PRED_L1) {
+    const int qx = mv0[2 * b], qy = mv0[2 * b + 1];
+    qpel_stage<TB>(s, ref0, width, height, width, x0 + (qx >> 2), y0 + (qy >> 2), bw, bh);
+    qpel_half_grid<TB>(s, bw, bh);
+    const QpelTaps t = qpel_taps(qx & 3, qy & 3);
+#pragma unroll
+    for (int k = 0; k < G::GPL; k++) p4[k] = qpel_pred4<TB>(s, P.px0[k], P.py[k], t);
+  }
+  if (md != ME_PRED_L0) {
+    const int qx = mv1[2 * b], qy = mv1[2 * b + 1];
+    // the reads of hg above precede the first barrier of this qpel_half_grid,
+    // its writes to hg follow the second
+    qpel_stage<TB>(s, ref1, width, height, width, x0 + (qx >> 2), y0 + (qy >> 2), bw, bh);
+    qpel_half_grid<TB>(s, bw, bh);
+    const QpelTaps t = qpel_taps(qx & 3, qy & 3);
+#pragma unroll
+    for (int k = 0; k < G::GPL; k++) {
+      const uint32_t c = qpel_pred4<TB>(s, P.px0[k], P.py[k], t);
+      p4[k] = md == ME_PRED_L1 ? c : avg4(p4[k], c);
+    }
+  }
+
+  const size_t n = (size_t)width * height;
+  unsigned long long sq = 0;
+  uint32_t mxv = 0;
+#pragma unroll
+  for (int k = 0; k < G::GPL; k++) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      if (P.mask[k] >> (8 * e) & 1) {
+        const size_t i = (size_t)(y0 + P.py[k]) * width + x0 + P.px0[k] + e;
+        const int m = (int)(p4[k] >> (8 * e) & 0xFF);
+        const int r = ref0[i], c = cur[i];
+        const int d = m - c;
+        sq += (unsigned long long)(d * d);
+        mxv = max(mxv, (uint32_t)max(m, c));
+        if (write_planes) {
+          out5[i] = (uint8_t)r;
+          out5[n + i] = (uint8_t)c;
+          out5[2 * n + i] = (uint8_t)m;
+          out5[3 * n + i] = (uint8_t)abs(r - c);
+          out5[4 * n + i] = (uint8_t)abs(d);
+        } else {
+          out5[i] = (uint8_t)m;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sq += __shfl_xor(sq, off, 64);
+    mxv = max(mxv, (uint32_t)__shfl_xor((int)mxv, off, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&stats[0], sq);
+    atomicMax(&stats[1], (unsigned long long)mxv);
+  }
+}
+
 int tile_of(int blk) { return blk <= 4 ? 4 : blk <= 8 ? 8 : blk <= 16 ? 16 : blk <= 32 ? 32 : 64; }
 
 template <int TB>
@@ -437,6 +696,61 @@ hipError_t launch_qpel_compensate(const uint8_t* ref, const uint8_t* cur, int wi
     ME_QPEL_COMP(64);
   }
 #undef ME_QPEL_COMP
+  return hipGetLastError();
+}
+
+hipError_t launch_bipred(const uint8_t* ref0, size_t ref0_frame_stride, const uint8_t* ref1,
+                         size_t ref1_frame_stride, const uint8_t* cur, size_t cur_frame_stride,
+                         int width, int height, int stride, int blk, bool ssd, int refine,
+                         int n_frames, const int16_t* q0_in, const int16_t* q1_in, int16_t* q0_out,
+                         int16_t* q1_out, uint8_t* mode_out, uint32_t* cost_out,
+                         uint32_t* cost3_out, hipStream_t stream) {
+  const int nbx = (width + blk - 1) / blk, nblk = nbx * ((height + blk - 1) / blk);
+  const dim3 grid((unsigned)nblk, (unsigned)n_frames);
+#define ME_BIPRED_K(TB, SSD)                                                                    \
+  hipLaunchKernelGGL((me_bipred_kernel<TB, SSD>), grid, dim3(QpelGeom<TB>::NT), 0, stream, ref0, \
+                     ref0_frame_stride, ref1, ref1_frame_stride, cur, cur_frame_stride, width,  \
+                     height, stride, blk, nbx, nblk, refine, q0_in, q1_in, q0_out, q1_out,      \
+                     mode_out, cost_out, cost3_out)
+#define ME_BIPRED(TB)                \
+  case TB:                           \
+    if (ssd)                         \
+      ME_BIPRED_K(TB, true);         \
+    else                             \
+      ME_BIPRED_K(TB, false);        \
+    break
+  switch (tile_of(blk)) {
+    ME_BIPRED(4);
+    ME_BIPRED(8);
+    ME_BIPRED(16);
+    ME_BIPRED(32);
+    ME_BIPRED(64);
+  }
+#undef ME_BIPRED
+#undef ME_BIPRED_K
+  return hipGetLastError();
+}
+
+hipError_t launch_bipred_compensate(const uint8_t* ref0, const uint8_t* ref1, const uint8_t* cur,
+                                    int width, int height, int blk, const int16_t* mv0,
+                                    const int16_t* mv1, const uint8_t* mode, uint8_t* out5,
+                                    int write_planes, unsigned long long* stats,
+                                    hipStream_t stream) {
+  const int nbx = (width + blk - 1) / blk, nblk = nbx * ((height + blk - 1) / blk);
+#define ME_BIPRED_COMP(TB)                                                                      \
+  case TB:                                                                                      \
+    hipLaunchKernelGGL(me_bipred_compensate_kernel<TB>, dim3((unsigned)nblk),                   \
+                       dim3(QpelGeom<TB>::NT), 0, stream, ref0, ref1, cur, width, height, blk,  \
+                       nbx, mv0, mv1, mode, out5, write_planes, stats);                         \
+    break
+  switch (tile_of(blk)) {
+    ME_BIPRED_COMP(4);
+    ME_BIPRED_COMP(8);
+    ME_BIPRED_COMP(16);
+    ME_BIPRED_COMP(32);
+    ME_BIPRED_COMP(64);
+  }
+#undef ME_BIPRED_COMP
   return hipGetLastError();
 }
 

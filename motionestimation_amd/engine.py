@@ -222,6 +222,82 @@ class Engine:
                                                    _ptr(mc)), self._h)
         return mc
 
+    # ---- bi-prediction (include/me.h "bi-predictive mode decision") ----
+    @staticmethod
+    def _planes3(ref0, ref1, cur):
+        ref0 = np.ascontiguousarray(ref0, dtype=np.uint8)
+        ref1 = np.ascontiguousarray(ref1, dtype=np.uint8)
+        cur = np.ascontiguousarray(cur, dtype=np.uint8)
+        if ref0.ndim != 2 or ref0.shape != cur.shape or ref1.shape != cur.shape:
+            raise MEError(_lib.ME_EINVAL,
+                          f"plane shapes {ref0.shape} / {ref1.shape} vs {cur.shape}")
+        return ref0, ref1, cur
+
+    @staticmethod
+    def _field(mv, n, what):
+        mv = np.ascontiguousarray(mv, np.int16)
+        if mv.size != 2 * n:
+            raise MEError(_lib.ME_EINVAL, f"{what} of {mv.size // 2} records for {n} blocks")
+        return mv
+
+    def bipred(self, ref0, ref1, cur, blk: int, mv_q0, mv_q1, cost="ssd", refine=True,
+               stride=None):
+        """Per block: the costs of ref0 at mv_q0, ref1 at mv_q1 and their
+        rounded average (jointly refined by a quarter step with refine), and
+        the cheapest mode.  Returns (mv0 int16 [nblocks, 2], mv1 int16
+        [nblocks, 2], mode uint8 [nblocks] (ME_PRED_L0 / L1 / BI), cost uint32
+        [nblocks], cost3 uint32 [nblocks, 3] = (c0, c1, cb))."""
+        ref0, ref1, cur = self._planes3(ref0, ref1, cur)
+        h, w = cur.shape
+        n = num_blocks(w, h, blk) if blk > 0 else 0
+        q0, q1 = self._field(mv_q0, n, "mv_q0"), self._field(mv_q1, n, "mv_q1")
+        m = max(n, 1)
+        o0, o1 = np.zeros((m, 2), np.int16), np.zeros((m, 2), np.int16)
+        mode, cst, c3 = np.zeros(m, np.uint8), np.zeros(m, np.uint32), np.zeros((m, 3), np.uint32)
+        check(_lib.lib().me_bipred(self._h, _ptr(ref0), _ptr(ref1), _ptr(cur), w, h, stride or w,
+                                   blk, cost_code(cost), int(bool(refine)), _ptr(q0), _ptr(q1),
+                                   _ptr(o0), _ptr(o1), _ptr(mode), _ptr(cst), _ptr(c3)), self._h)
+        return o0[:n], o1[:n], mode[:n], cst[:n], c3[:n]
+
+    def full_search_bipred(self, ref0, ref1, cur, blk: int, span: int, cost="ssd", stride=None):
+        """Both searches, both quarter-pel refinements and bipred(refine=True)
+        back to back on the device.  Returns (mv0, mv1, mode, cost)."""
+        ref0, ref1, cur = self._planes3(ref0, ref1, cur)
+        h, w = cur.shape
+        n = num_blocks(w, h, blk) if blk > 0 else 0
+        m = max(n, 1)
+        o0, o1 = np.zeros((m, 2), np.int16), np.zeros((m, 2), np.int16)
+        mode, cst = np.zeros(m, np.uint8), np.zeros(m, np.uint32)
+        check(_lib.lib().me_full_search_bipred(self._h, _ptr(ref0), _ptr(ref1), _ptr(cur), w, h,
+                                               stride or w, blk, span, cost_code(cost), _ptr(o0),
+                                               _ptr(o1), _ptr(mode), _ptr(cst)), self._h)
+        return o0[:n], o1[:n], mode[:n], cst[:n]
+
+    def compensate_planes_bipred(self, ref0, ref1, cur, blk: int, mv0, mv1, mode):
+        """compensate_planes_qpel with two references and a mode per block:
+        [ref0, cur, mc, |ref0-cur|, |mc-cur|] (5H, W) and PSNR."""
+        ref0, ref1, cur = self._planes3(ref0, ref1, cur)
+        mv0, mv1 = np.ascontiguousarray(mv0, np.int16), np.ascontiguousarray(mv1, np.int16)
+        mode = np.ascontiguousarray(mode, np.uint8)
+        h, w = cur.shape
+        out = np.zeros((5 * h, w), np.uint8)
+        psnr = ctypes.c_double()
+        check(_lib.lib().me_compensate_planes_bipred(
+            self._h, _ptr(ref0), _ptr(ref1), _ptr(cur), w, h, blk, _ptr(mv0), _ptr(mv1),
+            _ptr(mode), _ptr(out), ctypes.byref(psnr)), self._h)
+        return out, psnr.value
+
+    def motion_compensate_bipred(self, ref0, ref1, blk: int, mv0, mv1, mode):
+        ref0, ref1, _ = self._planes3(ref0, ref1, ref0)
+        mv0, mv1 = np.ascontiguousarray(mv0, np.int16), np.ascontiguousarray(mv1, np.int16)
+        mode = np.ascontiguousarray(mode, np.uint8)
+        h, w = ref0.shape
+        mc = np.zeros_like(ref0)
+        check(_lib.lib().me_motion_compensate_bipred(
+            self._h, _ptr(ref0), _ptr(ref1), w, h, blk, _ptr(mv0), _ptr(mv1), _ptr(mode),
+            _ptr(mc)), self._h)
+        return mc
+
     def search_pairs(self, frames, pairs, blk: int, span: int, cost="ssd"):
         """Search many (ref, cur) frame pairs in one pipelined call.
 
@@ -363,6 +439,48 @@ class Engine:
                 (q_t if q_t is not None else mv_t).data_ptr(),
                 cost_t.data_ptr() if cost_t is not None else None,
                 stream if stream is not None else _current_stream())
+
+        def run():
+            s = fn(*args)
+            if s:
+                check(s, ctx)
+        return run
+
+    def bipred_device(self, ref0_t, ref1_t, cur_t, blk: int, cost, q0_t, q1_t, mode_t,
+                      out0_t=None, out1_t=None, cost_t=None, cost3_t=None, refine=True,
+                      stream=None, width=None, height=None):
+        """Enqueue the bi-prediction of resident frames (me_bipred_device):
+        ref0_t / ref1_t / cur_t are uint8 tensors (H, pitch) of one row pitch or
+        batches [F, H, pitch], q0_t / q1_t the quarter-pel fields int16
+        [F * nblocks, 2], out0_t / out1_t the results (None: in place), mode_t
+        uint8 [F * nblocks], cost_t uint32/int32 [F * nblocks] or None, cost3_t
+        [F * nblocks, 3] or None."""
+        self.prepared_bipred(ref0_t, ref1_t, cur_t, blk, cost, q0_t, q1_t, mode_t, out0_t, out1_t,
+                             cost_t, cost3_t, refine, stream, width, height)()
+
+    def prepared_bipred(self, ref0_t, ref1_t, cur_t, blk, cost, q0_t, q1_t, mode_t, out0_t=None,
+                        out1_t=None, cost_t=None, cost3_t=None, refine=True, stream=None,
+                        width=None, height=None):
+        """Zero-argument callable enqueueing bipred_device(...) with these buffers."""
+        dims = {ref0_t.dim(), ref1_t.dim(), cur_t.dim()}
+        es = cur_t.element_size()
+        if dims not in ({2}, {3}) or len({t.shape[0] for t in (ref0_t, ref1_t, cur_t)}) != 1 or \
+                len({t.stride(-2) for t in (ref0_t, ref1_t, cur_t)}) != 1:
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {tuple(ref0_t.shape)} / "
+                          f"{tuple(ref1_t.shape)} / {tuple(cur_t.shape)} or row pitches differ")
+        batch = cur_t.dim() == 3
+        frames = cur_t.shape[0] if batch else 1
+        fs = [t.stride(0) * es if batch else 0 for t in (ref0_t, ref1_t, cur_t)]
+        h = height if height else cur_t.shape[-2]
+        w = width if width else cur_t.shape[-1]
+        opt = lambda t: t.data_ptr() if t is not None else None
+        fn, ctx = _lib.lib().me_bipred_device, self._h
+        args = (ctx, ref0_t.data_ptr(), fs[0], ref1_t.data_ptr(), fs[1], cur_t.data_ptr(), fs[2],
+                w, h, cur_t.stride(-2) * es, blk, cost_code(cost), int(bool(refine)), frames,
+                q0_t.data_ptr(), q1_t.data_ptr(),
+                (out0_t if out0_t is not None else q0_t).data_ptr(),
+                (out1_t if out1_t is not None else q1_t).data_ptr(), mode_t.data_ptr(),
+                opt(cost_t), opt(cost3_t), stream if stream is not None else _current_stream())
 
         def run():
             s = fn(*args)
