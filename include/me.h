@@ -490,6 +490,126 @@ me_status me_compensate_planes_bipred(me_ctx* ctx, const uint8_t* ref0, const ui
                                       const int16_t* mv0, const int16_t* mv1, const uint8_t* mode,
                                       uint8_t* out5, double* psnr);
 
+/* ---- variable-block-size partition search with mode decision ----
+ * One pass over the candidates of every B x B macroblock yields the best
+ * integer vector of the macroblock, of its two B x h halves, its two h x B
+ * halves and its four h x h quarters (h = B / 2), and the cheapest of the four
+ * shapes.  No reference counterpart; parity is against the numpy restatement
+ * tests/partition_ref.py.  Exact integers (DESIGN.md "Partition search"):
+ *   - grids: nbx = ceil(W/B), nby = ceil(H/B), nhx = ceil(W/h), nhy = ceil(H/h).
+ *     Macroblock (bx, by) has its top-left at (x0, y0) = (bx B, by B) and is
+ *     clipped to the frame: bw x bh.
+ *   - partitions of a macroblock: the nominal rectangles clipped to the frame;
+ *     empty ones do not exist.  2Nx2N: the macroblock; 2NxN: two B x h (top,
+ *     bottom); Nx2N: two h x B (left, right); NxN: four h x h.
+ *   - each shape's field is stored in the raster order of its own grid over
+ *     the frame (the non-empty partitions are exactly the grids' cells):
+ *     2Nx2N nbx x nby; 2NxN nbx x nhy, cell (bx, 2 by + j) is half j of
+ *     macroblock (bx, by); Nx2N nhx x nby; NxN nhx x nhy.
+ *   - candidates of a macroblock: exactly me_full_search's at block size B,
+ *     top-left (cx, cy) with cx in [max(0, x0 - S), min(W, x0 + bw + S) - bw],
+ *     cy likewise.  Every partition of the macroblock is costed at the same
+ *     displacements d = (cx - x0, cy - y0), its pixels against the reference
+ *     pixels at + d (always inside the frame).  The displacement set is the
+ *     macroblock's own, not the one a B/2 search would give the sub-block (the
+ *     two differ where the frame clamps).
+ *   - winner per partition: the first minimum in raster order of the
+ *     displacements (dy outer, dx inner, strict <); its cost is its SAD.  So
+ *     the 2Nx2N field and costs are me_full_search's at (B, S, SAD) bit for
+ *     bit, and the four NxN records of a full-size macroblock whose window is
+ *     not clamped on any side are me_full_search's at (B/2, S).
+ *   - mode: J(2Nx2N) = c + lambda, J(2NxN) = sum of halves + 2 lambda,
+ *     J(Nx2N) = sum of halves + 2 lambda, J(NxN) = sum of quarters + 4 lambda,
+ *     the sums over the non-empty partitions, the lambda multipliers always the
+ *     nominal 1, 2, 2, 4.  Modes are tried in the order 0, 1, 2, 3 and a later
+ *     one replaces the best only if strictly smaller.  mode: one byte per
+ *     macroblock; mode_cost: its J.  lambda <= ME_PART_MAX_LAMBDA, so J cannot
+ *     overflow (B = 32: 261,120 + 4 * 2^24 < 2^32).
+ *   - leaf field: on the NxN grid; cell (hx, hy) belongs to macroblock
+ *     (hx / 2, hy / 2) of mode m and takes the vector of the partition that
+ *     contains it: m = 0 mv_2nx2n[by][bx], m = 1 mv_2nxn[hy][bx], m = 2
+ *     mv_nx2n[by][hx], m = 3 mv_nxn[hy][hx].  It is an ordinary integer field
+ *     of block size h: me_motion_compensate, me_compensate_planes,
+ *     me_refine_qpel* and me_mv_write take it unchanged at block_size = B / 2,
+ *     and sum |mc - cur| over the frame = sum over the macroblocks of
+ *     J - lambda * (nominal vector count of the mode).
+ *   - limits: B in {8, 16, 32} and S <= ME_PART_MAX_RANGE (ME_EUNSUPPORTED
+ *     otherwise); ME_COST_SAD only (SSD and SSIM: ME_EUNSUPPORTED; follow-ups,
+ *     SSD belongs on the matrix cores); whole frames on the context's first
+ *     device only (a context with several devices: ME_EUNSUPPORTED; there is no
+ *     stripe entry point); stride * height < 2^31. */
+typedef enum me_part_mode {
+  ME_PART_2Nx2N = 0,
+  ME_PART_2NxN = 1,
+  ME_PART_Nx2N = 2,
+  ME_PART_NxN = 3
+} me_part_mode;
+#define ME_PART_MAX_RANGE 128
+#define ME_PART_MAX_LAMBDA (1u << 24)
+
+/* The records of a partition search, one array per grid (host arrays for the
+ * host entry points, device arrays for the device ones).  The mv_* arrays and
+ * mode are required; the cost_* arrays and mode_cost may be NULL. */
+typedef struct me_part_fields {
+  int16_t* mv_2nx2n;   /* [nby][nbx][2] */
+  int16_t* mv_2nxn;    /* [nhy][nbx][2] */
+  int16_t* mv_nx2n;    /* [nby][nhx][2] */
+  int16_t* mv_nxn;     /* [nhy][nhx][2] */
+  uint32_t* cost_2nx2n;
+  uint32_t* cost_2nxn;
+  uint32_t* cost_nx2n;
+  uint32_t* cost_nxn;
+  uint8_t* mode;       /* [nby][nbx] me_part_mode */
+  uint32_t* mode_cost; /* [nby][nbx] J of the chosen mode */
+} me_part_fields;
+
+/* counts[0..4) = cells of the 2Nx2N, 2NxN, Nx2N and NxN grids.  Host only. */
+me_status me_partition_counts(int width, int height, int block_size, int counts[4]);
+
+enum { ME_PART_KERNEL_GENERIC = 0, ME_PART_KERNEL_FAST = 1 };
+/* The kernel that takes the frame's full-size macroblocks: ME_PART_KERNEL_FAST
+ * (the packed-u16 quadrant kernel: B = 16, S <= 64, width and row pitch
+ * multiples of 4, at least one full-size macroblock; it also needs planes and
+ * frame strides that are multiples of 4 bytes, which the launch checks on top)
+ * or ME_PART_KERNEL_GENERIC; -1 for arguments the search rejects.  Chosen by
+ * B, S and the row alignment only, never by the frame size.  Clipped
+ * macroblocks of any frame run on the generic kernel.  Host only; the launch
+ * consults this same function. */
+int me_partition_kernel_variant(int width, int height, int stride, int block_size,
+                                int search_range);
+
+/* Search n_frames >= 1 whole frames of one geometry on HBM-resident planes of
+ * ctx's first device, laid out as for me_refine_qpel_device: frame f's planes
+ * at d_ref + f * ref_frame_stride and d_cur + f * cur_frame_stride bytes, its
+ * records at each pointer of d_out + f * that grid's count (x 2 for vectors).
+ * d_out is a HOST struct of device pointers, read before the call returns.
+ * Asynchronous on `stream`, ordered after the context's previous search like
+ * any search; uses no context scratch, so it can be captured
+ * (me_capture_begin) without a warm-up call. */
+me_status me_partition_search_device(me_ctx* ctx, const uint8_t* d_ref, size_t ref_frame_stride,
+                                     const uint8_t* d_cur, size_t cur_frame_stride, int width,
+                                     int height, int stride, int block_size, int search_range,
+                                     me_cost cost, uint32_t lambda, int n_frames,
+                                     const me_part_fields* d_out, void* stream);
+
+/* The same on host planes of row pitch `stride` into host arrays, synchronous. */
+me_status me_partition_search(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int width,
+                              int height, int stride, int block_size, int search_range,
+                              me_cost cost, uint32_t lambda, const me_part_fields* out);
+
+/* The leaf field of n_frames searched frames on the device: d_in's four mv_*
+ * arrays and mode (the costs are not read), d_leaf_mv [n_frames][nhy][nhx][2].
+ * Asynchronous on `stream`, ordered like a search.  A mode byte above 3 is
+ * read as ME_PART_NxN (not checked: the field is on the device). */
+me_status me_partition_leaf_field_device(me_ctx* ctx, int width, int height, int block_size,
+                                         int n_frames, const me_part_fields* d_in,
+                                         int16_t* d_leaf_mv, void* stream);
+
+/* The leaf field of one frame on the host: no context and no GPU.  ME_EINVAL
+ * for a mode byte above 3. */
+me_status me_partition_leaf_field(int width, int height, int block_size,
+                                  const me_part_fields* in, int16_t* leaf_mv);
+
 /* ---- frame-pair streaming ---- */
 
 /* Pinned (page-locked) host memory.  Frames that live in it are DMAed

@@ -6,10 +6,13 @@ include/me.h); this package is the host-side mirror of the reference's
 interface over that ABI.  There is no CPU fallback.
 """
 from ._lib import (ME_COST_SAD, ME_COST_SSD, ME_COST_SSIM, ME_ECOMM, ME_EDEVICE,  # noqa: F401
-                   ME_BIPRED_MAX_Q, ME_PRED_BI, ME_PRED_L0, ME_PRED_L1, ME_QPEL_MAX_MV, MEError,
+                   ME_BIPRED_MAX_Q, ME_PART_2Nx2N, ME_PART_2NxN, ME_PART_KERNEL_FAST,
+                   ME_PART_KERNEL_GENERIC, ME_PART_MAX_LAMBDA, ME_PART_MAX_RANGE, ME_PART_Nx2N,
+                   ME_PART_NxN, ME_PRED_BI, ME_PRED_L0, ME_PRED_L1, ME_QPEL_MAX_MV, MEError,
                    build)
-from .engine import (Engine, candidate_count, num_blocks, pinned_frames,  # noqa: F401
-                     last_search_path, plan_stripes, set_kernel_path, version)
+from .engine import (Engine, PartitionFields, candidate_count, num_blocks,  # noqa: F401
+                     partition_counts, partition_kernel_variant, partition_leaf_field,
+                     pinned_frames, last_search_path, plan_stripes, set_kernel_path, version)
 from . import io  # noqa: F401
 from .reference_api import (Block, PredictionFrame, create_prediction_frame,  # noqa: F401
                             find_best_blk_mse, find_best_blk_ssim, find_best_blks,

@@ -27,6 +27,9 @@ ME_MAX_BLOCK, ME_MAX_RANGE = 64, 1024
 ME_QPEL_MAX_MV = 8000  # integer input vectors of the quarter-pel refinement
 ME_PRED_L0, ME_PRED_L1, ME_PRED_BI = 0, 1, 2  # me_pred_mode
 ME_BIPRED_MAX_Q = 32766  # input quarter-pel vectors of the bi-prediction
+ME_PART_2Nx2N, ME_PART_2NxN, ME_PART_Nx2N, ME_PART_NxN = 0, 1, 2, 3  # me_part_mode
+ME_PART_MAX_RANGE, ME_PART_MAX_LAMBDA = 128, 1 << 24
+ME_PART_KERNEL_GENERIC, ME_PART_KERNEL_FAST = 0, 1  # me_partition_kernel_variant
 
 # Every symbol include/me.h declares, with (restype, argtypes).
 _u8p = ctypes.c_void_p
@@ -112,6 +115,18 @@ _SIGS = {
     "me_compensate_planes_bipred": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, _u8p] +
                                     [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4 +
                                     [ctypes.POINTER(ctypes.c_double)]),
+    "me_partition_counts": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int)]),
+    "me_partition_kernel_variant": (ctypes.c_int, [ctypes.c_int] * 5),
+    # (the me_part_fields arguments are ctypes.byref(engine.PartFields))
+    "me_partition_search_device": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_size_t, _u8p,
+                                                  ctypes.c_size_t] + [ctypes.c_int] * 6 +
+                                   [ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p,
+                                    ctypes.c_void_p]),
+    "me_partition_search": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] + [ctypes.c_int] * 6 +
+                            [ctypes.c_uint32, ctypes.c_void_p]),
+    "me_partition_leaf_field_device": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 +
+                                       [ctypes.c_void_p] * 3),
+    "me_partition_leaf_field": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2),
     "me_mv_read_header": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
     "me_mv_read": (ctypes.c_int, [ctypes.c_char_p] + [ctypes.c_void_p] * 4),
 }

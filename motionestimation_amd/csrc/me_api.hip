@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "me_internal.h"
+#include "me_partition.h"
 
 using me::Dev;
 
@@ -1455,6 +1456,149 @@ me_status me_compensate_planes_bipred(me_ctx* c, const uint8_t* ref0, const uint
                                       uint8_t* out5, double* psnr) {
   if (!cur) return fail(c, ME_EINVAL, "null cur");
   return compensate_bipred(c, ref0, ref1, cur, width, height, blk, mv0, mv1, mode, out5, 1, psnr);
+}
+
+// ---- partition search (me_partition.hip, me_partition_plan.cpp) ----
+
+// The search's own argument rules; *n: the four grids' cell counts.
+static me_status check_partition(me_ctx* c, const void* ref, const void* cur, int width, int height,
+                                 int stride, int blk, int range, me_cost cost, uint32_t lambda,
+                                 const me_part_fields* out, int n[4]) {
+  if (!c) return ME_EINVAL;
+  if (!ref || !cur || !out) return fail(c, ME_EINVAL, "null plane or field pointer");
+  if (!out->mv_2nx2n || !out->mv_2nxn || !out->mv_nx2n || !out->mv_nxn || !out->mode)
+    return fail(c, ME_EINVAL, "null partition vector field or mode array");
+  if (cost != ME_COST_SSD && cost != ME_COST_SAD && cost != ME_COST_SSIM)
+    return fail(c, ME_EINVAL, "cost %d", (int)cost);
+  const char* why = "";
+  const me_status s = me::partition_check(width, height, stride, blk, range, &why);
+  if (s != ME_OK) return fail(c, s, "%s (%dx%d pitch %d, B %d, S %d)", why, width, height, stride,
+                              blk, range);
+  if (cost != ME_COST_SAD)
+    return fail(c, ME_EUNSUPPORTED, "partition search costs SAD only");
+  if (lambda > ME_PART_MAX_LAMBDA)
+    return fail(c, ME_EINVAL, "lambda %u above ME_PART_MAX_LAMBDA", lambda);
+  if (c->devs.size() > 1)
+    return fail(c, ME_EUNSUPPORTED, "partition search on %zu devices (one device only)",
+                c->devs.size());
+  if (me_partition_counts(width, height, blk, n) != ME_OK)
+    return fail(c, ME_EINVAL, "frame %dx%d", width, height);
+  return ME_OK;
+}
+
+// Enqueue the search of n_frames frames on s after the device's previous
+// search (not while capturing: me_graph_launch orders the graph).
+static me_status partition_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rfs,
+                              const uint8_t* d_cur, size_t cfs, int width, int height, int stride,
+                              int blk, int range, uint32_t lambda, int n_frames,
+                              const me_part_fields& out, hipStream_t s) {
+  if (!me::capturing(s)) {
+    me_status st = me::order_on(c, d, s);
+    if (st != ME_OK) return st;
+  }
+  // the kernel me_partition_kernel_variant names; its LDS DMA also needs
+  // planes and frame strides that are multiples of 4 bytes
+  const bool fast =
+      me_partition_kernel_variant(width, height, stride, blk, range) == ME_PART_KERNEL_FAST &&
+      ((uintptr_t)d_ref | (uintptr_t)d_cur | (n_frames > 1 ? rfs | cfs : 0)) % 4 == 0;
+  const hipError_t e = me::launch_partition_search(d_ref, rfs, d_cur, cfs, width, height, stride,
+                                                   blk, range, lambda, n_frames, fast, out, s);
+  if (e != hipSuccess)
+    return me::fail(c, ME_EDEVICE, "partition search launch: %s", hipGetErrorString(e));
+  return ME_OK;
+}
+
+me_status me_partition_search_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
+                                     const uint8_t* d_cur, size_t cur_frame_stride, int width,
+                                     int height, int stride, int blk, int range, me_cost cost,
+                                     uint32_t lambda, int n_frames, const me_part_fields* d_out,
+                                     void* stream) {
+  if (!c) return ME_EINVAL;
+  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
+  int n[4];
+  me_status s = check_partition(c, d_ref, d_cur, width, height, stride, blk, range, cost, lambda,
+                                d_out, n);
+  if (s != ME_OK) return s;
+  // frames must not overlap and a plane stack stays below 2 GiB, as in
+  // me_refine_qpel_device
+  const unsigned long long fb = (unsigned long long)stride * height;
+  if (n_frames > 1 && (ref_frame_stride < fb || cur_frame_stride < fb))
+    return fail(c, ME_EINVAL, "frame strides %zu / %zu below a frame's %llu bytes",
+                ref_frame_stride, cur_frame_stride, fb);
+  const unsigned long long rb = (unsigned long long)(n_frames - 1) * ref_frame_stride + fb;
+  const unsigned long long cb = (unsigned long long)(n_frames - 1) * cur_frame_stride + fb;
+  if (rb >= (1ull << 31) || cb >= (1ull << 31))
+    return fail(c, ME_EUNSUPPORTED, "batch of %llu / %llu bytes (limit 2 GiB)", rb, cb);
+  c->err[0] = 0;
+  Dev& d = c->devs[0];
+  return partition_on(c, d, d_ref, ref_frame_stride, d_cur, cur_frame_stride, width, height,
+                      stride, blk, range, lambda, n_frames, *d_out, (hipStream_t)stream);
+}
+
+me_status me_partition_search(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
+                              int height, int stride, int blk, int range, me_cost cost,
+                              uint32_t lambda, const me_part_fields* out) {
+  int n[4];
+  me_status s = check_partition(c, ref, cur, width, height, stride, blk, range, cost, lambda, out, n);
+  if (s != ME_OK) return s;
+  c->err[0] = 0;
+  Dev& d = c->devs[0];
+  // records in d.rec: the four vector fields, the four cost fields, the mode
+  // costs (4 bytes per cell each), then the mode bytes
+  const size_t cells = (size_t)n[0] + n[1] + n[2] + n[3];
+  const size_t bytes = 8 * cells + 4 * (size_t)n[0] + (size_t)n[0];
+  if ((s = upload_pair(c, d, ref, cur, width, height, stride, (bytes + 7) / 8)) != ME_OK) return s;
+  me_part_fields D;
+  uint8_t* p = d.rec;
+  int16_t** mv[4] = {&D.mv_2nx2n, &D.mv_2nxn, &D.mv_nx2n, &D.mv_nxn};
+  uint32_t** co[4] = {&D.cost_2nx2n, &D.cost_2nxn, &D.cost_nx2n, &D.cost_nxn};
+  for (int g = 0; g < 4; g++) *mv[g] = reinterpret_cast<int16_t*>(p), p += 4 * (size_t)n[g];
+  for (int g = 0; g < 4; g++) *co[g] = reinterpret_cast<uint32_t*>(p), p += 4 * (size_t)n[g];
+  D.mode_cost = reinterpret_cast<uint32_t*>(p), p += 4 * (size_t)n[0];
+  D.mode = p;
+  if ((s = partition_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, range, lambda, 1, D,
+                        d.stream)) != ME_OK)
+    return s;
+  int16_t* const hmv[4] = {out->mv_2nx2n, out->mv_2nxn, out->mv_nx2n, out->mv_nxn};
+  uint32_t* const hco[4] = {out->cost_2nx2n, out->cost_2nxn, out->cost_nx2n, out->cost_nxn};
+  for (int g = 0; g < 4; g++) {
+    HIPCHK(c, hipMemcpyAsync(hmv[g], *mv[g], 4 * (size_t)n[g], hipMemcpyDeviceToHost, d.stream));
+    if (hco[g])
+      HIPCHK(c, hipMemcpyAsync(hco[g], *co[g], 4 * (size_t)n[g], hipMemcpyDeviceToHost, d.stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(out->mode, D.mode, (size_t)n[0], hipMemcpyDeviceToHost, d.stream));
+  if (out->mode_cost)
+    HIPCHK(c, hipMemcpyAsync(out->mode_cost, D.mode_cost, 4 * (size_t)n[0], hipMemcpyDeviceToHost,
+                             d.stream));
+  HIPCHK(c, hipStreamSynchronize(d.stream));
+  return ME_OK;
+}
+
+me_status me_partition_leaf_field_device(me_ctx* c, int width, int height, int blk, int n_frames,
+                                         const me_part_fields* d_in, int16_t* d_leaf_mv,
+                                         void* stream) {
+  if (!c) return ME_EINVAL;
+  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
+  if (!d_in || !d_leaf_mv || !d_in->mv_2nx2n || !d_in->mv_2nxn || !d_in->mv_nx2n ||
+      !d_in->mv_nxn || !d_in->mode)
+    return fail(c, ME_EINVAL, "null partition vector field, mode array or leaf field");
+  const char* why = "";
+  const me_status s = me::partition_check(width, height, width, blk, 0, &why);
+  if (s != ME_OK) return fail(c, s, "%s (%dx%d, B %d)", why, width, height, blk);
+  if (c->devs.size() > 1)
+    return fail(c, ME_EUNSUPPORTED, "partition leaf field on %zu devices (one device only)",
+                c->devs.size());
+  c->err[0] = 0;
+  Dev& d = c->devs[0];
+  hipStream_t st = (hipStream_t)stream;
+  if (!me::capturing(st)) {
+    const me_status o = me::order_on(c, d, st);
+    if (o != ME_OK) return o;
+  }
+  const hipError_t e = me::launch_partition_leaf(width, height, blk, n_frames, *d_in, d_leaf_mv, st);
+  if (e != hipSuccess)
+    return me::fail(c, ME_EDEVICE, "partition leaf field launch: %s", hipGetErrorString(e));
+  return ME_OK;
 }
 
 }  // extern "C"

@@ -4,6 +4,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "me.h"
 #include "me_dispatch.h"
 #include "me_geom.h"
 #include "me_mfma_geom.h"
@@ -22,6 +25,22 @@ constexpr int SCHED_ERR = 31;
 // since the words were last zeroed: live lane-tasks, all lane-tasks, items
 // whose bound was bypassed, items.
 constexpr int SCHED_PRUNE = 24;
+
+// The packed key of a candidate: the unsigned minimum of keys is the smallest
+// cost and, among equal costs, the first displacement in raster order.
+__device__ __forceinline__ uint64_t make_key(uint32_t cost, int dx, int dy) {
+  return ((uint64_t)cost << 32) | ((uint32_t)(dy + 32768) << 16) | (uint32_t)(dx + 32768);
+}
+
+// Compile-time loop: every index is a constant, so register arrays indexed by
+// it never fall back to scratch (plain #pragma unroll gives up on big bodies).
+template <int I, int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    static_for<I + 1, N>(f);
+  }
+}
 
 // Write block `out`'s MV from a merged 64-bit key (cost << 32 | (dy + 32768)
 // << 16 | (dx + 32768)): one 4-byte store of the (mvx, mvy) int16 pair when the
@@ -87,6 +106,18 @@ size_t ssim_scratch(const SearchArgs& p);
 hipError_t launch_compensate(const uint8_t* ref, const uint8_t* cur, int width, int height,
                              int blk, const int16_t* mv, uint8_t* out5, int write_planes,
                              unsigned long long* stats, hipStream_t stream);
+
+// Partition search (me_partition.hip; geometry in me_partition.h).
+// n_frames whole frames; out: device pointers (host struct).  fast: the
+// full-size macroblocks on the packed-u16 kernel (me_partition_kernel_variant
+// said FAST and the planes are 4-byte aligned), the clipped ones on the generic
+// kernel; otherwise every macroblock on the generic kernel.
+hipError_t launch_partition_search(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
+                                   size_t cur_frame_stride, int width, int height, int stride,
+                                   int blk, int range, uint32_t lambda, int n_frames, bool fast,
+                                   const me_part_fields& out, hipStream_t stream);
+hipError_t launch_partition_leaf(int width, int height, int blk, int n_frames,
+                                 const me_part_fields& in, int16_t* leaf, hipStream_t stream);
 
 // Quarter-pel refinement and sub-pel compensation (me_subpel.hip).
 // launch_qpel_refine: n_frames whole frames (planes at + f * frame stride,

@@ -44,20 +44,6 @@
 
 namespace me {
 
-__device__ __forceinline__ uint64_t make_key(uint32_t cost, int dx, int dy) {
-  return ((uint64_t)cost << 32) | ((uint32_t)(dy + 32768) << 16) | (uint32_t)(dx + 32768);
-}
-
-// Compile-time loop: every index is a constant, so register arrays indexed by
-// it never fall back to scratch (plain #pragma unroll gives up on big bodies).
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {

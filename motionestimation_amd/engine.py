@@ -44,6 +44,87 @@ def plan_stripes(width: int, height: int, blk: int, span: int, shards: int) -> l
     return list(out)
 
 
+def partition_counts(width: int, height: int, blk: int) -> tuple:
+    """Cells of the partition search's four grids (me_partition_counts):
+    (2Nx2N, 2NxN, Nx2N, NxN)."""
+    out = (ctypes.c_int * 4)()
+    check(_lib.lib().me_partition_counts(width, height, blk, out))
+    return tuple(out)
+
+
+def partition_kernel_variant(width: int, height: int, stride: int, blk: int, span: int) -> int:
+    """The kernel that takes the frame's full-size macroblocks
+    (me_partition_kernel_variant): ME_PART_KERNEL_FAST, ME_PART_KERNEL_GENERIC,
+    or -1 for arguments the search rejects."""
+    return int(_lib.lib().me_partition_kernel_variant(width, height, stride, blk, span))
+
+
+class PartFields(ctypes.Structure):
+    """include/me.h me_part_fields."""
+    _fields_ = [(n, ctypes.c_void_p) for n in
+                ("mv_2nx2n", "mv_2nxn", "mv_nx2n", "mv_nxn", "cost_2nx2n", "cost_2nxn",
+                 "cost_nx2n", "cost_nxn", "mode", "mode_cost")]
+
+
+class PartitionFields:
+    """The records of a partition search: mv (four int16 [cells, 2] fields in
+    the order 2Nx2N, 2NxN, Nx2N, NxN), cost (four uint32 [cells], or None),
+    mode (uint8 per macroblock) and mode_cost (uint32 per macroblock, or None).
+    numpy arrays from the host entry points, torch tensors ([F * cells, ...],
+    frame-major) for the device ones."""
+
+    def __init__(self, mv, cost, mode, mode_cost):
+        self.mv, self.cost, self.mode, self.mode_cost = list(mv), cost, mode, mode_cost
+
+    def struct(self) -> PartFields:
+        ptr = (lambda a: a.ctypes.data) if isinstance(self.mode, np.ndarray) else \
+            (lambda a: a.data_ptr())
+        opt = lambda a: ptr(a) if a is not None else None
+        cost = self.cost if self.cost is not None else [None] * 4
+        return PartFields(*[ptr(a) for a in self.mv], *[opt(a) for a in cost], ptr(self.mode),
+                          opt(self.mode_cost))
+
+    @classmethod
+    def host(cls, width: int, height: int, blk: int) -> "PartitionFields":
+        n = partition_counts(width, height, blk)
+        return cls([np.zeros((k, 2), np.int16) for k in n], [np.zeros(k, np.uint32) for k in n],
+                   np.zeros(n[0], np.uint8), np.zeros(n[0], np.uint32))
+
+    @classmethod
+    def device(cls, width: int, height: int, blk: int, frames: int = 1, device="cuda"):
+        import torch
+        n = partition_counts(width, height, blk)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        return cls([z((frames * k, 2), torch.int16) for k in n],
+                   [z((frames * k,), torch.int32) for k in n],
+                   z((frames * n[0],), torch.uint8), z((frames * n[0],), torch.int32))
+
+    def numpy(self) -> "PartitionFields":
+        """Host copy of device fields (costs as uint32)."""
+        u = lambda t: t.cpu().numpy().view(np.uint32)
+        return PartitionFields([t.cpu().numpy() for t in self.mv],
+                               [u(t) for t in self.cost] if self.cost is not None else None,
+                               self.mode.cpu().numpy(),
+                               u(self.mode_cost) if self.mode_cost is not None else None)
+
+
+def partition_leaf_field(width: int, height: int, blk: int, fields: PartitionFields):
+    """The leaf field (int16 [nhx * nhy, 2], block size blk / 2) of one frame's
+    host fields, on the host (me_partition_leaf_field: no context, no GPU)."""
+    n = partition_counts(width, height, blk)
+    f = PartitionFields([np.ascontiguousarray(a, np.int16) for a in fields.mv], None,
+                        np.ascontiguousarray(fields.mode, np.uint8), None)
+    for a, k in zip(f.mv, n):
+        if a.size != 2 * k:
+            raise MEError(_lib.ME_EINVAL, f"field of {a.size // 2} records for {k} cells")
+    if f.mode.size != n[0]:
+        raise MEError(_lib.ME_EINVAL, f"{f.mode.size} modes for {n[0]} macroblocks")
+    leaf = np.zeros((n[3], 2), np.int16)
+    st = f.struct()
+    check(_lib.lib().me_partition_leaf_field(width, height, blk, ctypes.byref(st), _ptr(leaf)))
+    return leaf
+
+
 _PATH_CODES = {"auto": 0, "valu": 1, "tiles": 2, "lean": 3, "prepass": 4}
 
 
@@ -298,6 +379,26 @@ class Engine:
             _ptr(mc)), self._h)
         return mc
 
+    # ---- partition search (include/me.h "partition search") ----
+    def partition_search(self, ref, cur, blk: int, span: int, lam: int = 0, cost="sad",
+                         width=None) -> "PartitionFields":
+        """Best vector of every macroblock, of its halves and of its quarters,
+        and the cheapest of the four shapes at Lagrangian weight lam
+        (me_partition_search) on (H, pitch) uint8 planes; width (default: the
+        pitch) names the frame's columns.  Returns PartitionFields of numpy
+        arrays."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        cur = np.ascontiguousarray(cur, dtype=np.uint8)
+        if ref.ndim != 2 or ref.shape != cur.shape:
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {ref.shape} vs {cur.shape}")
+        h, pitch = ref.shape
+        w = width or pitch
+        out = PartitionFields.host(w, h, blk)
+        st = out.struct()
+        check(_lib.lib().me_partition_search(self._h, _ptr(ref), _ptr(cur), w, h, pitch, blk, span,
+                                             cost_code(cost), lam, ctypes.byref(st)), self._h)
+        return out
+
     def search_pairs(self, frames, pairs, blk: int, span: int, cost="ssd"):
         """Search many (ref, cur) frame pairs in one pipelined call.
 
@@ -487,6 +588,53 @@ class Engine:
             if s:
                 check(s, ctx)
         return run
+
+    def partition_search_device(self, ref_t, cur_t, blk: int, span: int, lam: int, fields,
+                                cost="sad", stream=None, width=None, height=None):
+        """Enqueue the partition search of resident frames
+        (me_partition_search_device): ref_t / cur_t are uint8 tensors (H, pitch)
+        or batches [F, H, pitch], fields a PartitionFields of torch tensors
+        (PartitionFields.device).  width / height default to the tensors' last
+        two dimensions; the row pitch and the frame strides are the tensors'."""
+        self.prepared_partition_search(ref_t, cur_t, blk, span, lam, fields, cost, stream, width,
+                                       height)()
+
+    def prepared_partition_search(self, ref_t, cur_t, blk, span, lam, fields, cost="sad",
+                                  stream=None, width=None, height=None):
+        """Zero-argument callable enqueueing partition_search_device(...) with these buffers."""
+        if ref_t.dim() not in (2, 3) or ref_t.dim() != cur_t.dim() or \
+                ref_t.stride(-2) != cur_t.stride(-2) or \
+                (ref_t.dim() == 3 and ref_t.shape[0] != cur_t.shape[0]):
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {tuple(ref_t.shape)} / "
+                          f"{tuple(cur_t.shape)} or row pitches differ")
+        es = ref_t.element_size()
+        frames = ref_t.shape[0] if ref_t.dim() == 3 else 1
+        rfs = ref_t.stride(0) * es if ref_t.dim() == 3 else 0
+        cfs = cur_t.stride(0) * es if cur_t.dim() == 3 else 0
+        h = height if height else ref_t.shape[-2]
+        w = width if width else ref_t.shape[-1]
+        st = fields.struct()
+        fn, ctx = _lib.lib().me_partition_search_device, self._h
+        args = (ctx, ref_t.data_ptr(), rfs, cur_t.data_ptr(), cfs, w, h, ref_t.stride(-2) * es, blk,
+                span, cost_code(cost), lam, frames, ctypes.byref(st),
+                stream if stream is not None else _current_stream())
+
+        def run():
+            s = fn(*args)
+            if s:
+                check(s, ctx)
+        run.fields = st  # keep the pointer struct alive with the callable
+        return run
+
+    def partition_leaf_field_device(self, width: int, height: int, blk: int, fields, leaf_t,
+                                    frames: int = 1, stream=None):
+        """Enqueue the leaf field of `frames` searched frames
+        (me_partition_leaf_field_device): leaf_t int16 [frames * nhx * nhy, 2],
+        an ordinary integer field of block size blk / 2."""
+        st = fields.struct()
+        check(_lib.lib().me_partition_leaf_field_device(
+            self._h, width, height, blk, frames, ctypes.byref(st), leaf_t.data_ptr(),
+            stream if stream is not None else _current_stream()), self._h)
 
     # ---- multi-process stripes: the one exchange step in native code ----
     @staticmethod
