@@ -610,6 +610,103 @@ me_status me_partition_leaf_field_device(me_ctx* ctx, int width, int height, int
 me_status me_partition_leaf_field(int width, int height, int block_size,
                                   const me_part_fields* in, int16_t* leaf_mv);
 
+/* ---- rate-constrained motion search: J = SAD + lambda * bits(mv - predictor) ----
+ * The integer full search and the quarter-pel refinement with the cost of
+ * coding the vector in the objective.  No reference counterpart; parity is
+ * against the numpy restatement tests/rd_ref.py.  Exact integers (DESIGN.md
+ * "Rate-constrained search"):
+ *   - bits(v) = 2 * floor(log2(2 |v| + 1)) + 1, the length of the signed
+ *     exp-Golomb code se(v): 0 -> 1; +-1 -> 3; +-2, +-3 -> 5; +-4 .. +-7 -> 7.
+ *   - a predictor p = (px, py) per block is int16 in QUARTER-pel units, the
+ *     units of me_refine_qpel's output: a previous frame's refined field is a
+ *     predictor as it stands.  A NULL predictor array means all zero.  Any
+ *     int16 value is legal: |4 d - p| <= 4 * 1024 + 32,767, so bits <= 33 per
+ *     component and R <= 66.
+ *   - integer search: for block b and displacement d = (dx, dy),
+ *     R(d) = bits(4 dx - px) + bits(4 dy - py), J(d) = SAD(d) + lambda * R(d).
+ *     The candidates are me_full_search's at (B, S), clamping included; the
+ *     winner is the first minimum of J in raster order (dy outer, dx inner,
+ *     strict <).  Per block: the vector (int16, integer units), block_cost = J,
+ *     block_dist = SAD, block_bits = R (one byte).  lambda <= ME_RD_MAX_LAMBDA,
+ *     so J < 2^32 (64 * 64 * 255 + 66 * 2^24).  With lambda = 0 the vectors and
+ *     costs are me_full_search's at SAD bit for bit, whatever the predictor.
+ *   - refinement: me_refine_qpel's procedure (stages, candidate order, centre
+ *     carried, strict <) on Jq(q) = cost(P(q)) + lambda * (bits(qx - px) +
+ *     bits(qy - py)), cost SAD or SSD.  Outputs mv_q, block_cost = Jq,
+ *     block_dist = cost(P(mv_q)).  With lambda = 0 it is me_refine_qpel bit for
+ *     bit.  Jq < 2^32 for SSD too (64 * 64 * 255^2 + 66 * 2^24).
+ *   - limits: the search costs ME_COST_SAD only (SSD and SSIM:
+ *     ME_EUNSUPPORTED; follow-ups), B in [1, ME_MAX_BLOCK], S <=
+ *     ME_RD_MAX_RANGE (ME_EUNSUPPORTED above); the refinement has
+ *     me_refine_qpel's limits.  Both: whole frames on the context's first
+ *     device only (a context with several devices or repeated ids:
+ *     ME_EUNSUPPORTED; no stripe entry point); lambda above ME_RD_MAX_LAMBDA or
+ *     a negative range: ME_EINVAL. */
+#define ME_RD_MAX_RANGE 128
+#define ME_RD_MAX_LAMBDA (1u << 24)
+/* Largest lambda of the fast kernel: its 32-bit lane key J << 6 | index needs
+ * J <= 65,280 + 66 lambda < 2^26. */
+#define ME_RD_FAST_MAX_LAMBDA 1015811u
+
+/* bits(v) as defined above, for any int.  Host only. */
+int me_mv_bits(int v);
+
+enum { ME_RD_KERNEL_GENERIC = 0, ME_RD_KERNEL_FAST = 1 };
+/* The kernel that takes the frame's full-size blocks: ME_RD_KERNEL_FAST (B =
+ * 16, S <= 64, width and row pitch multiples of 4, at least one full-size
+ * block, lambda <= ME_RD_FAST_MAX_LAMBDA; it also needs planes and frame
+ * strides that are multiples of 4 bytes, which the launch checks on top) or
+ * ME_RD_KERNEL_GENERIC; -1 for arguments the search rejects.  Chosen by B, S,
+ * the row alignment and lambda only, never by the frame size.  Clipped blocks
+ * of any frame run on the generic kernel.  Host only; the launch consults this
+ * same function. */
+int me_rd_kernel_variant(int width, int height, int stride, int block_size, int search_range,
+                         uint32_t lambda);
+
+/* Search n_frames >= 1 whole frames of one geometry on HBM-resident planes of
+ * ctx's first device, laid out as for me_refine_qpel_device: frame f's planes
+ * at d_ref + f * ref_frame_stride and d_cur + f * cur_frame_stride bytes, its
+ * predictors at d_pred_q + 2 * f * nblk, its results at d_mv_xy + 2 * f * nblk
+ * and d_block_cost / d_block_dist / d_block_bits + f * nblk.  d_pred_q (all
+ * zero), d_block_dist and d_block_bits may be NULL.  Asynchronous on `stream`,
+ * ordered after the context's previous search like any search; uses no context
+ * scratch, so it can be captured (me_capture_begin) without a warm-up call. */
+me_status me_rd_search_device(me_ctx* ctx, const uint8_t* d_ref, size_t ref_frame_stride,
+                              const uint8_t* d_cur, size_t cur_frame_stride, int width,
+                              int height, int stride, int block_size, int search_range,
+                              me_cost cost, uint32_t lambda, int n_frames,
+                              const int16_t* d_pred_q, int16_t* d_mv_xy, uint32_t* d_block_cost,
+                              uint32_t* d_block_dist, uint8_t* d_block_bits, void* stream);
+
+/* The same on host planes of row pitch `stride` into host arrays, synchronous. */
+me_status me_rd_search(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int width,
+                       int height, int stride, int block_size, int search_range, me_cost cost,
+                       uint32_t lambda, const int16_t* pred_q, int16_t* mv_xy,
+                       uint32_t* block_cost, uint32_t* block_dist, uint8_t* block_bits);
+
+/* me_refine_qpel_device / me_refine_qpel with the rate term: d_pred_q laid out
+ * like d_mv_xy (NULL: all zero), d_block_cost = Jq and d_block_dist = the
+ * distortion at d_mv_q (each may be NULL). */
+me_status me_refine_qpel_rd_device(me_ctx* ctx, const uint8_t* d_ref, size_t ref_frame_stride,
+                                   const uint8_t* d_cur, size_t cur_frame_stride, int width,
+                                   int height, int stride, int block_size, me_cost cost,
+                                   uint32_t lambda, int n_frames, const int16_t* d_pred_q,
+                                   const int16_t* d_mv_xy, int16_t* d_mv_q,
+                                   uint32_t* d_block_cost, uint32_t* d_block_dist, void* stream);
+me_status me_refine_qpel_rd(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int width,
+                            int height, int stride, int block_size, me_cost cost, uint32_t lambda,
+                            const int16_t* pred_q, const int16_t* mv_xy, int16_t* mv_q,
+                            uint32_t* block_cost, uint32_t* block_dist);
+
+/* me_rd_search then me_refine_qpel_rd back to back on the device with the same
+ * predictor and lambda, as me_full_search_qpel does: the integer field never
+ * visits the host.  ME_COST_SAD (the search's limit).  One context device.
+ * pred_q and block_cost may be NULL. */
+me_status me_full_search_rd_qpel(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int width,
+                                 int height, int stride, int block_size, int search_range,
+                                 me_cost cost, uint32_t lambda, const int16_t* pred_q,
+                                 int16_t* mv_q, uint32_t* block_cost);
+
 /* ---- frame-pair streaming ---- */
 
 /* Pinned (page-locked) host memory.  Frames that live in it are DMAed

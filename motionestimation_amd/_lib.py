@@ -30,6 +30,9 @@ ME_BIPRED_MAX_Q = 32766  # input quarter-pel vectors of the bi-prediction
 ME_PART_2Nx2N, ME_PART_2NxN, ME_PART_Nx2N, ME_PART_NxN = 0, 1, 2, 3  # me_part_mode
 ME_PART_MAX_RANGE, ME_PART_MAX_LAMBDA = 128, 1 << 24
 ME_PART_KERNEL_GENERIC, ME_PART_KERNEL_FAST = 0, 1  # me_partition_kernel_variant
+ME_RD_MAX_RANGE, ME_RD_MAX_LAMBDA = 128, 1 << 24  # rate-constrained search
+ME_RD_FAST_MAX_LAMBDA = 1015811  # the fast kernel's largest lambda
+ME_RD_KERNEL_GENERIC, ME_RD_KERNEL_FAST = 0, 1  # me_rd_kernel_variant
 
 # Every symbol include/me.h declares, with (restype, argtypes).
 _u8p = ctypes.c_void_p
@@ -127,6 +130,20 @@ _SIGS = {
     "me_partition_leaf_field_device": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 +
                                        [ctypes.c_void_p] * 3),
     "me_partition_leaf_field": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2),
+    "me_mv_bits": (ctypes.c_int, [ctypes.c_int]),
+    "me_rd_kernel_variant": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_uint32]),
+    "me_rd_search_device": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_size_t, _u8p,
+                                           ctypes.c_size_t] + [ctypes.c_int] * 6 +
+                            [ctypes.c_uint32, ctypes.c_int] + [ctypes.c_void_p] * 6),
+    "me_rd_search": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] + [ctypes.c_int] * 6 +
+                     [ctypes.c_uint32] + [ctypes.c_void_p] * 5),
+    "me_refine_qpel_rd_device": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_size_t, _u8p,
+                                                ctypes.c_size_t] + [ctypes.c_int] * 5 +
+                                 [ctypes.c_uint32, ctypes.c_int] + [ctypes.c_void_p] * 6),
+    "me_refine_qpel_rd": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] + [ctypes.c_int] * 5 +
+                          [ctypes.c_uint32] + [ctypes.c_void_p] * 5),
+    "me_full_search_rd_qpel": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] + [ctypes.c_int] * 6 +
+                               [ctypes.c_uint32] + [ctypes.c_void_p] * 3),
     "me_mv_read_header": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
     "me_mv_read": (ctypes.c_int, [ctypes.c_char_p] + [ctypes.c_void_p] * 4),
 }

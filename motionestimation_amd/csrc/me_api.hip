@@ -20,6 +20,7 @@
 
 #include "me_internal.h"
 #include "me_partition.h"
+#include "me_rd.h"
 
 using me::Dev;
 
@@ -1598,6 +1599,237 @@ me_status me_partition_leaf_field_device(me_ctx* c, int width, int height, int b
   const hipError_t e = me::launch_partition_leaf(width, height, blk, n_frames, *d_in, d_leaf_mv, st);
   if (e != hipSuccess)
     return me::fail(c, ME_EDEVICE, "partition leaf field launch: %s", hipGetErrorString(e));
+  return ME_OK;
+}
+
+// ---- rate-constrained search (me_rd.hip, me_rd_plan.cpp, me_subpel.hip) ----
+
+// The argument rules shared by the search and the refinement entry points.
+static me_status check_rd_ctx(me_ctx* c, uint32_t lambda, const char* what) {
+  if (lambda > ME_RD_MAX_LAMBDA)
+    return fail(c, ME_EINVAL, "lambda %u above ME_RD_MAX_LAMBDA", lambda);
+  if (c->devs.size() > 1)
+    return fail(c, ME_EUNSUPPORTED, "%s on %zu devices (one device only)", what, c->devs.size());
+  return ME_OK;
+}
+
+// The search's own argument rules.
+static me_status check_rd(me_ctx* c, const void* ref, const void* cur, int width, int height,
+                          int stride, int blk, int range, me_cost cost, uint32_t lambda,
+                          const void* mv, const void* block_cost) {
+  if (!c) return ME_EINVAL;
+  if (!ref || !cur || !mv || !block_cost)
+    return fail(c, ME_EINVAL, "null plane, vector or cost pointer");
+  if (cost != ME_COST_SSD && cost != ME_COST_SAD && cost != ME_COST_SSIM)
+    return fail(c, ME_EINVAL, "cost %d", (int)cost);
+  const char* why = "";
+  const me_status s = me::rd_check(width, height, stride, blk, range, lambda, &why);
+  if (s != ME_OK)
+    return fail(c, s, "%s (%dx%d pitch %d, B %d, S %d, lambda %u)", why, width, height, stride,
+                blk, range, lambda);
+  if (cost != ME_COST_SAD)
+    return fail(c, ME_EUNSUPPORTED, "rate-constrained search costs SAD only");
+  return check_rd_ctx(c, lambda, "rate-constrained search");
+}
+
+// Frames must not overlap and a plane stack stays below 2 GiB, as in
+// me_refine_qpel_device.
+static me_status check_frame_strides(me_ctx* c, int stride, int height, int n_frames, size_t rfs,
+                                     size_t cfs) {
+  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
+  const unsigned long long fb = (unsigned long long)stride * height;
+  if (n_frames > 1 && (rfs < fb || cfs < fb))
+    return fail(c, ME_EINVAL, "frame strides %zu / %zu below a frame's %llu bytes", rfs, cfs, fb);
+  const unsigned long long rb = (unsigned long long)(n_frames - 1) * rfs + fb;
+  const unsigned long long cb = (unsigned long long)(n_frames - 1) * cfs + fb;
+  if (rb >= (1ull << 31) || cb >= (1ull << 31))
+    return fail(c, ME_EUNSUPPORTED, "batch of %llu / %llu bytes (limit 2 GiB)", rb, cb);
+  return ME_OK;
+}
+
+// Enqueue the search of n_frames frames on s after the device's previous
+// search (not while capturing: me_graph_launch orders the graph).
+static me_status rd_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rfs, const uint8_t* d_cur,
+                       size_t cfs, int width, int height, int stride, int blk, int range,
+                       uint32_t lambda, int n_frames, const int16_t* d_pred, int16_t* d_mv,
+                       uint32_t* d_cost, uint32_t* d_dist, uint8_t* d_bits, hipStream_t s) {
+  if (!me::capturing(s)) {
+    me_status st = me::order_on(c, d, s);
+    if (st != ME_OK) return st;
+  }
+  // the kernel me_rd_kernel_variant names; its LDS DMA also needs planes and
+  // frame strides that are multiples of 4 bytes
+  const bool fast =
+      me_rd_kernel_variant(width, height, stride, blk, range, lambda) == ME_RD_KERNEL_FAST &&
+      ((uintptr_t)d_ref | (uintptr_t)d_cur | (n_frames > 1 ? rfs | cfs : 0)) % 4 == 0;
+  const hipError_t e = me::launch_rd_search(d_ref, rfs, d_cur, cfs, width, height, stride, blk,
+                                            range, lambda, n_frames, fast, d_pred, d_mv, d_cost,
+                                            d_dist, d_bits, s);
+  if (e != hipSuccess)
+    return me::fail(c, ME_EDEVICE, "rate-constrained search launch: %s", hipGetErrorString(e));
+  return ME_OK;
+}
+
+static me_status refine_rd_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rfs,
+                              const uint8_t* d_cur, size_t cfs, int width, int height, int stride,
+                              int blk, me_cost cost, uint32_t lambda, int n_frames,
+                              const int16_t* d_pred, const int16_t* d_mv, int16_t* d_q,
+                              uint32_t* d_cost, uint32_t* d_dist, hipStream_t s) {
+  if (!me::capturing(s)) {
+    me_status st = me::order_on(c, d, s);
+    if (st != ME_OK) return st;
+  }
+  const hipError_t e = me::launch_qpel_refine_rd(d_ref, rfs, d_cur, cfs, width, height, stride,
+                                                 blk, cost == ME_COST_SSD, lambda, n_frames,
+                                                 d_pred, d_mv, d_q, d_cost, d_dist, s);
+  if (e != hipSuccess)
+    return me::fail(c, ME_EDEVICE, "rate-constrained refinement launch: %s",
+                    hipGetErrorString(e));
+  return ME_OK;
+}
+
+me_status me_rd_search_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
+                              const uint8_t* d_cur, size_t cur_frame_stride, int width,
+                              int height, int stride, int blk, int range, me_cost cost,
+                              uint32_t lambda, int n_frames, const int16_t* d_pred_q,
+                              int16_t* d_mv_xy, uint32_t* d_block_cost, uint32_t* d_block_dist,
+                              uint8_t* d_block_bits, void* stream) {
+  me_status s = check_rd(c, d_ref, d_cur, width, height, stride, blk, range, cost, lambda,
+                         d_mv_xy, d_block_cost);
+  if (s != ME_OK) return s;
+  if ((s = check_frame_strides(c, stride, height, n_frames, ref_frame_stride,
+                               cur_frame_stride)) != ME_OK)
+    return s;
+  c->err[0] = 0;
+  return rd_on(c, c->devs[0], d_ref, ref_frame_stride, d_cur, cur_frame_stride, width, height,
+               stride, blk, range, lambda, n_frames, d_pred_q, d_mv_xy, d_block_cost,
+               d_block_dist, d_block_bits, (hipStream_t)stream);
+}
+
+// d.rec as [pred | mv | cost | dist] of nb blocks (4 bytes each per block),
+// then one byte per block; pred uploaded (zeros for a null predictor).
+struct RdRec {
+  int16_t *pred, *mv;
+  uint32_t *cost, *dist;
+  uint8_t* bits;
+};
+static me_status rd_records(me_ctx* c, Dev& d, size_t nb, const int16_t* pred_q, RdRec* r) {
+  r->pred = reinterpret_cast<int16_t*>(d.rec);
+  r->mv = reinterpret_cast<int16_t*>(d.rec + 4 * nb);
+  r->cost = reinterpret_cast<uint32_t*>(d.rec + 8 * nb);
+  r->dist = reinterpret_cast<uint32_t*>(d.rec + 12 * nb);
+  r->bits = d.rec + 16 * nb;
+  if (pred_q)
+    HIPCHK(c, hipMemcpyAsync(r->pred, pred_q, nb * 4, hipMemcpyHostToDevice, d.stream));
+  else
+    r->pred = nullptr;
+  return ME_OK;
+}
+
+me_status me_rd_search(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width, int height,
+                       int stride, int blk, int range, me_cost cost, uint32_t lambda,
+                       const int16_t* pred_q, int16_t* mv_xy, uint32_t* block_cost,
+                       uint32_t* block_dist, uint8_t* block_bits) {
+  me_status s = check_rd(c, ref, cur, width, height, stride, blk, range, cost, lambda, mv_xy,
+                         block_cost);
+  if (s != ME_OK) return s;
+  c->err[0] = 0;
+  Dev& d = c->devs[0];
+  const size_t nb = (size_t)me_num_blocks(width, height, blk);
+  if ((s = upload_pair(c, d, ref, cur, width, height, stride, (17 * nb + 7) / 8)) != ME_OK)
+    return s;
+  RdRec r;
+  if ((s = rd_records(c, d, nb, pred_q, &r)) != ME_OK) return s;
+  if ((s = rd_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, range, lambda, 1, r.pred,
+                 r.mv, r.cost, r.dist, r.bits, d.stream)) != ME_OK)
+    return s;
+  HIPCHK(c, hipMemcpyAsync(mv_xy, r.mv, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipMemcpyAsync(block_cost, r.cost, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  if (block_dist)
+    HIPCHK(c, hipMemcpyAsync(block_dist, r.dist, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  if (block_bits)
+    HIPCHK(c, hipMemcpyAsync(block_bits, r.bits, nb, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipStreamSynchronize(d.stream));
+  return ME_OK;
+}
+
+me_status me_refine_qpel_rd_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
+                                   const uint8_t* d_cur, size_t cur_frame_stride, int width,
+                                   int height, int stride, int blk, me_cost cost, uint32_t lambda,
+                                   int n_frames, const int16_t* d_pred_q, const int16_t* d_mv_xy,
+                                   int16_t* d_mv_q, uint32_t* d_block_cost,
+                                   uint32_t* d_block_dist, void* stream) {
+  if (!c) return ME_EINVAL;
+  me_status s = check_args(c, d_ref, d_cur, width, height, stride, blk, 0, cost, d_mv_xy);
+  if (s != ME_OK) return s;
+  if ((s = check_qpel(c, cost, d_mv_q)) != ME_OK) return s;
+  if ((s = check_rd_ctx(c, lambda, "rate-constrained refinement")) != ME_OK) return s;
+  if ((s = check_frame_strides(c, stride, height, n_frames, ref_frame_stride,
+                               cur_frame_stride)) != ME_OK)
+    return s;
+  c->err[0] = 0;
+  return refine_rd_on(c, c->devs[0], d_ref, ref_frame_stride, d_cur, cur_frame_stride, width,
+                      height, stride, blk, cost, lambda, n_frames, d_pred_q, d_mv_xy, d_mv_q,
+                      d_block_cost, d_block_dist, (hipStream_t)stream);
+}
+
+me_status me_refine_qpel_rd(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
+                            int height, int stride, int blk, me_cost cost, uint32_t lambda,
+                            const int16_t* pred_q, const int16_t* mv_xy, int16_t* mv_q,
+                            uint32_t* block_cost, uint32_t* block_dist) {
+  me_status s = check_args(c, ref, cur, width, height, stride, blk, 0, cost, mv_xy);
+  if (s != ME_OK) return s;
+  if ((s = check_qpel(c, cost, mv_q)) != ME_OK) return s;
+  if ((s = check_rd_ctx(c, lambda, "rate-constrained refinement")) != ME_OK) return s;
+  const size_t nb = (size_t)me_num_blocks(width, height, blk);
+  for (size_t i = 0; i < 2 * nb; i++)
+    if (mv_xy[i] > ME_QPEL_MAX_MV || mv_xy[i] < -ME_QPEL_MAX_MV)
+      return fail(c, ME_EINVAL, "block %zu: vector component %d beyond ME_QPEL_MAX_MV (%d)", i / 2,
+                  (int)mv_xy[i], ME_QPEL_MAX_MV);
+  c->err[0] = 0;
+  Dev& d = c->devs[0];
+  if ((s = upload_pair(c, d, ref, cur, width, height, stride, (17 * nb + 7) / 8)) != ME_OK)
+    return s;
+  RdRec r;
+  if ((s = rd_records(c, d, nb, pred_q, &r)) != ME_OK) return s;
+  HIPCHK(c, hipMemcpyAsync(r.mv, mv_xy, nb * 4, hipMemcpyHostToDevice, d.stream));
+  if ((s = refine_rd_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, cost, lambda, 1,
+                        r.pred, r.mv, r.mv, r.cost, r.dist, d.stream)) != ME_OK)
+    return s;
+  HIPCHK(c, hipMemcpyAsync(mv_q, r.mv, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  if (block_cost)
+    HIPCHK(c, hipMemcpyAsync(block_cost, r.cost, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  if (block_dist)
+    HIPCHK(c, hipMemcpyAsync(block_dist, r.dist, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipStreamSynchronize(d.stream));
+  return ME_OK;
+}
+
+me_status me_full_search_rd_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
+                                 int height, int stride, int blk, int range, me_cost cost,
+                                 uint32_t lambda, const int16_t* pred_q, int16_t* mv_q,
+                                 uint32_t* block_cost) {
+  // (block_cost is optional here: the search's own cost array is d.rec's)
+  me_status s = check_rd(c, ref, cur, width, height, stride, blk, range, cost, lambda, mv_q, mv_q);
+  if (s != ME_OK) return s;
+  c->err[0] = 0;
+  Dev& d = c->devs[0];
+  const size_t nb = (size_t)me_num_blocks(width, height, blk);
+  if ((s = upload_pair(c, d, ref, cur, width, height, stride, (17 * nb + 7) / 8)) != ME_OK)
+    return s;
+  RdRec r;
+  if ((s = rd_records(c, d, nb, pred_q, &r)) != ME_OK) return s;
+  if ((s = rd_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, range, lambda, 1, r.pred,
+                 r.mv, r.cost, nullptr, nullptr, d.stream)) != ME_OK)
+    return s;
+  // the searched vectors stay inside the window (|m| <= ME_RD_MAX_RANGE): refine in place
+  if ((s = refine_rd_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, cost, lambda, 1,
+                        r.pred, r.mv, r.mv, r.cost, nullptr, d.stream)) != ME_OK)
+    return s;
+  HIPCHK(c, hipMemcpyAsync(mv_q, r.mv, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  if (block_cost)
+    HIPCHK(c, hipMemcpyAsync(block_cost, r.cost, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipStreamSynchronize(d.stream));
   return ME_OK;
 }
 

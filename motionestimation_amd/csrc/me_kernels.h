@@ -127,6 +127,25 @@ hipError_t launch_qpel_refine(const uint8_t* ref, size_t ref_frame_stride, const
                               size_t cur_frame_stride, int width, int height, int stride, int blk,
                               bool ssd, int n_frames, const int16_t* mv_in, int16_t* mv_out,
                               uint32_t* cost_out, hipStream_t stream);
+// launch_qpel_refine on cost + lambda * bits(q - pred) (include/me.h
+// "rate-constrained motion search"): pred laid out like mv_in, null = all zero;
+// cost_out (J) and dist_out (the cost at the result) may be null.
+hipError_t launch_qpel_refine_rd(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
+                                 size_t cur_frame_stride, int width, int height, int stride,
+                                 int blk, bool ssd, uint32_t lambda, int n_frames,
+                                 const int16_t* pred, const int16_t* mv_in, int16_t* mv_out,
+                                 uint32_t* cost_out, uint32_t* dist_out, hipStream_t stream);
+// Rate-constrained integer search (me_rd.hip; geometry in me_rd.h).  n_frames
+// whole frames, records and predictors (null: all zero) at + f * nblk (x 2 for
+// vectors); dist and bits may be null.  fast: the full-size blocks on the
+// packed-u16 kernel (me_rd_kernel_variant said FAST and the planes are 4-byte
+// aligned), the clipped ones on the generic kernel; otherwise every block on
+// the generic kernel.
+hipError_t launch_rd_search(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
+                            size_t cur_frame_stride, int width, int height, int stride, int blk,
+                            int range, uint32_t lambda, int n_frames, bool fast,
+                            const int16_t* pred, int16_t* mv, uint32_t* cost, uint32_t* dist,
+                            uint8_t* bits, hipStream_t stream);
 // launch_compensate with quarter-pel vectors and edge-replicated samples.
 hipError_t launch_qpel_compensate(const uint8_t* ref, const uint8_t* cur, int width, int height,
                                   int blk, const int16_t* mvq, uint8_t* out5, int write_planes,

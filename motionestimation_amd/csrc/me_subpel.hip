@@ -31,6 +31,7 @@
 
 #include "me.h"
 #include "me_kernels.h"
+#include "me_rd.h"
 
 namespace me {
 namespace {
@@ -335,6 +336,78 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_qpel_refine_kernel(
     mv_out[2 * rec] = (int16_t)(4 * mx + ox);
     mv_out[2 * rec + 1] = (int16_t)(4 * my + oy);
     if (cost_out) cost_out[rec] = best;
+  }
+}
+
+// me_qpel_refine_kernel on Jq(q) = cost(P(q)) + lambda (bits(qx - px) +
+// bits(qy - py)) against the block's quarter-pel predictor (include/me.h
+// "rate-constrained motion search"): the same stages, candidate order, carried
+// centre and strict <.  A kernel of its own, so the plain refinement's code and
+// registers stay as they are.  pred null: all zero; cost_out (Jq) and dist_out
+// (the cost at the result) may be null.
+template <int TB, bool SSD>
+__global__ __launch_bounds__(QpelGeom<TB>::NT) void me_qpel_refine_rd_kernel(
+    const uint8_t* __restrict__ ref, size_t ref_frame_stride, const uint8_t* __restrict__ cur,
+    size_t cur_frame_stride, int width, int height, int stride, int blk, int nbx, int nblk,
+    uint32_t lambda, const int16_t* pred, const int16_t* mv_in, int16_t* mv_out,
+    uint32_t* cost_out, uint32_t* dist_out) {
+  using G = QpelGeom<TB>;
+  __shared__ QpelLds<TB> s;
+  const int b = blockIdx.x, f = blockIdx.y;
+  const size_t rec = (size_t)f * nblk + b;
+  const int x0 = (b % nbx) * blk, y0 = (b / nbx) * blk;
+  const int bw = min(blk, width - x0), bh = min(blk, height - y0);
+  const int mx = mv_in[2 * rec], my = mv_in[2 * rec + 1];
+  // the centre relative to the predictor, in quarter units
+  const int ex = 4 * mx - (pred ? pred[2 * rec] : 0), ey = 4 * my - (pred ? pred[2 * rec + 1] : 0);
+  ref += (size_t)f * ref_frame_stride;
+  cur += (size_t)f * cur_frame_stride;
+
+  QpelPix<TB> P;
+  qpel_pixels<TB>(P, cur + (size_t)y0 * stride + x0, stride, bw, bh);
+  uint32_t cc = 0;
+  if (SSD) {
+#pragma unroll
+    for (int k = 0; k < G::GPL; k++) cc = __builtin_amdgcn_udot4(P.cur[k], P.cur[k], cc, false);
+  }
+  qpel_stage<TB>(s, ref, width, height, stride, x0 + mx, y0 + my, bw, bh);
+  qpel_half_grid<TB>(s, bw, bh);
+
+  auto rate = [&](int ox, int oy) {
+    return lambda * (uint32_t)(rd_bits(ex + ox) + rd_bits(ey + oy));
+  };
+  uint32_t c9[9];
+  int ox = 0, oy = 0;  // quarter offset of the best candidate from 4 * m
+  qpel_costs<TB, SSD, true>(s, P, cc, 0, 0, 2, c9);
+  uint32_t dist = c9[4], best = dist + rate(0, 0);
+#pragma unroll
+  for (int n = 0; n < 9; n++) {
+    const uint32_t j = c9[n] + rate(2 * (n % 3 - 1), 2 * (n / 3 - 1));
+    if (n != 4 && j < best) {
+      best = j;
+      dist = c9[n];
+      ox = 2 * (n % 3 - 1);
+      oy = 2 * (n / 3 - 1);
+    }
+  }
+  const int cx = ox, cy = oy;
+  qpel_costs<TB, SSD, false>(s, P, cc, cx, cy, 1, c9);
+#pragma unroll
+  for (int n = 0; n < 9; n++) {
+    if (n == 4) continue;
+    const uint32_t j = c9[n] + rate(cx + n % 3 - 1, cy + n / 3 - 1);
+    if (j < best) {
+      best = j;
+      dist = c9[n];
+      ox = cx + n % 3 - 1;
+      oy = cy + n / 3 - 1;
+    }
+  }
+  if (threadIdx.x == 0) {
+    mv_out[2 * rec] = (int16_t)(4 * mx + ox);
+    mv_out[2 * rec + 1] = (int16_t)(4 * my + oy);
+    if (cost_out) cost_out[rec] = best;
+    if (dist_out) dist_out[rec] = dist;
   }
 }
 
@@ -654,7 +727,46 @@ void refine_tb(bool ssd, dim3 grid, hipStream_t stream, const uint8_t* ref, size
                        cost_out);
 }
 
+template <int TB>
+void refine_rd_tb(bool ssd, dim3 grid, hipStream_t stream, const uint8_t* ref, size_t rfs,
+                  const uint8_t* cur, size_t cfs, int width, int height, int stride, int blk,
+                  int nbx, int nblk, uint32_t lambda, const int16_t* pred, const int16_t* mv_in,
+                  int16_t* mv_out, uint32_t* cost_out, uint32_t* dist_out) {
+  if (ssd)
+    hipLaunchKernelGGL((me_qpel_refine_rd_kernel<TB, true>), grid, dim3(QpelGeom<TB>::NT), 0,
+                       stream, ref, rfs, cur, cfs, width, height, stride, blk, nbx, nblk, lambda,
+                       pred, mv_in, mv_out, cost_out, dist_out);
+  else
+    hipLaunchKernelGGL((me_qpel_refine_rd_kernel<TB, false>), grid, dim3(QpelGeom<TB>::NT), 0,
+                       stream, ref, rfs, cur, cfs, width, height, stride, blk, nbx, nblk, lambda,
+                       pred, mv_in, mv_out, cost_out, dist_out);
+}
+
 }  // namespace
+
+hipError_t launch_qpel_refine_rd(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
+                                 size_t cur_frame_stride, int width, int height, int stride,
+                                 int blk, bool ssd, uint32_t lambda, int n_frames,
+                                 const int16_t* pred, const int16_t* mv_in, int16_t* mv_out,
+                                 uint32_t* cost_out, uint32_t* dist_out, hipStream_t stream) {
+  const int nbx = (width + blk - 1) / blk, nblk = nbx * ((height + blk - 1) / blk);
+  const dim3 grid((unsigned)nblk, (unsigned)n_frames);
+#define ME_QPEL_REFINE_RD(TB)                                                                   \
+  case TB:                                                                                      \
+    refine_rd_tb<TB>(ssd, grid, stream, ref, ref_frame_stride, cur, cur_frame_stride, width,    \
+                     height, stride, blk, nbx, nblk, lambda, pred, mv_in, mv_out, cost_out,     \
+                     dist_out);                                                                 \
+    break
+  switch (tile_of(blk)) {
+    ME_QPEL_REFINE_RD(4);
+    ME_QPEL_REFINE_RD(8);
+    ME_QPEL_REFINE_RD(16);
+    ME_QPEL_REFINE_RD(32);
+    ME_QPEL_REFINE_RD(64);
+  }
+#undef ME_QPEL_REFINE_RD
+  return hipGetLastError();
+}
 
 hipError_t launch_qpel_refine(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
                               size_t cur_frame_stride, int width, int height, int stride, int blk,

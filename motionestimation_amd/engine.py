@@ -59,6 +59,21 @@ def partition_kernel_variant(width: int, height: int, stride: int, blk: int, spa
     return int(_lib.lib().me_partition_kernel_variant(width, height, stride, blk, span))
 
 
+def mv_bits(v: int) -> int:
+    """Code length of a vector component difference (me_mv_bits): the signed
+    exp-Golomb length 2 floor(log2(2 |v| + 1)) + 1."""
+    return int(_lib.lib().me_mv_bits(v))
+
+
+def rd_kernel_variant(width: int, height: int, stride: int, blk: int, span: int, lam: int) -> int:
+    """The kernel that takes the frame's full-size blocks in a rate-constrained
+    search (me_rd_kernel_variant): ME_RD_KERNEL_FAST, ME_RD_KERNEL_GENERIC, or
+    -1 for arguments the search rejects."""
+    if not 0 <= lam < 1 << 32:
+        return -1
+    return int(_lib.lib().me_rd_kernel_variant(width, height, stride, blk, span, lam))
+
+
 class PartFields(ctypes.Structure):
     """include/me.h me_part_fields."""
     _fields_ = [(n, ctypes.c_void_p) for n in
@@ -399,6 +414,80 @@ class Engine:
                                              cost_code(cost), lam, ctypes.byref(st)), self._h)
         return out
 
+    # ---- rate-constrained search (include/me.h "rate-constrained motion search") ----
+    def _pred(self, pred, n):
+        if pred is None:
+            return None
+        pred = np.ascontiguousarray(pred, np.int16)
+        if pred.size != 2 * n:
+            raise MEError(_lib.ME_EINVAL, f"predictor of {pred.size // 2} records for {n} blocks")
+        return pred
+
+    def rd_search(self, ref, cur, blk: int, span: int, lam: int = 0, pred=None, cost="sad",
+                  width=None):
+        """The minimiser of SAD + lam * bits(4 mv - pred) per block
+        (me_rd_search) on (H, pitch) uint8 planes; pred int16 [nblocks, 2] in
+        quarter-pel units or None (all zero); width (default: the pitch) names
+        the frame's columns.  Returns (mv int16 [nblocks, 2], J uint32, SAD
+        uint32, bits uint8)."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        cur = np.ascontiguousarray(cur, dtype=np.uint8)
+        if ref.ndim != 2 or ref.shape != cur.shape:
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {ref.shape} vs {cur.shape}")
+        h, pitch = ref.shape
+        w = width or pitch
+        n = num_blocks(w, h, blk) if blk > 0 else 0
+        pred = self._pred(pred, n)
+        mv = np.zeros((max(n, 1), 2), np.int16)
+        j, d = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        r = np.zeros(max(n, 1), np.uint8)
+        check(_lib.lib().me_rd_search(self._h, _ptr(ref), _ptr(cur), w, h, pitch, blk, span,
+                                      cost_code(cost), lam, _ptr(pred) if pred is not None else None,
+                                      _ptr(mv), _ptr(j), _ptr(d), _ptr(r)), self._h)
+        return mv[:n], j[:n], d[:n], r[:n]
+
+    def refine_qpel_rd(self, ref, cur, blk: int, mv, lam: int = 0, pred=None, cost="ssd",
+                       stride=None):
+        """refine_qpel on cost + lam * bits(q - pred) (me_refine_qpel_rd).
+        Returns (mv_q int16 [nblocks, 2], Jq uint32, distortion uint32)."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        cur = np.ascontiguousarray(cur, dtype=np.uint8)
+        if ref.ndim != 2 or ref.shape != cur.shape:
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {ref.shape} vs {cur.shape}")
+        h, w = ref.shape
+        n = num_blocks(w, h, blk) if blk > 0 else 0
+        mv = np.ascontiguousarray(mv, np.int16)
+        if mv.size != 2 * n:
+            raise MEError(_lib.ME_EINVAL, f"mv of {mv.size // 2} records for {n} blocks")
+        pred = self._pred(pred, n)
+        q = np.zeros((max(n, 1), 2), np.int16)
+        j, d = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        check(_lib.lib().me_refine_qpel_rd(self._h, _ptr(ref), _ptr(cur), w, h, stride or w, blk,
+                                           cost_code(cost), lam,
+                                           _ptr(pred) if pred is not None else None, _ptr(mv),
+                                           _ptr(q), _ptr(j), _ptr(d)), self._h)
+        return q[:n], j[:n], d[:n]
+
+    def full_search_rd_qpel(self, ref, cur, blk: int, span: int, lam: int = 0, pred=None,
+                            cost="sad", stride=None):
+        """rd_search and refine_qpel_rd back to back on the device with one
+        predictor and lam (me_full_search_rd_qpel).  Returns (mv_q int16
+        [nblocks, 2] in quarter-pel units, Jq uint32 [nblocks])."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        cur = np.ascontiguousarray(cur, dtype=np.uint8)
+        if ref.ndim != 2 or ref.shape != cur.shape:
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {ref.shape} vs {cur.shape}")
+        h, w = ref.shape
+        n = num_blocks(w, h, blk) if blk > 0 else 0
+        pred = self._pred(pred, n)
+        q = np.zeros((max(n, 1), 2), np.int16)
+        j = np.zeros(max(n, 1), np.uint32)
+        check(_lib.lib().me_full_search_rd_qpel(self._h, _ptr(ref), _ptr(cur), w, h, stride or w,
+                                                blk, span, cost_code(cost), lam,
+                                                _ptr(pred) if pred is not None else None, _ptr(q),
+                                                _ptr(j)), self._h)
+        return q[:n], j[:n]
+
     def search_pairs(self, frames, pairs, blk: int, span: int, cost="ssd"):
         """Search many (ref, cur) frame pairs in one pipelined call.
 
@@ -625,6 +714,65 @@ class Engine:
                 check(s, ctx)
         run.fields = st  # keep the pointer struct alive with the callable
         return run
+
+    def rd_search_device(self, ref_t, cur_t, blk: int, span: int, lam: int, mv_t, cost_t,
+                         dist_t=None, bits_t=None, pred_t=None, cost="sad", stream=None,
+                         width=None, height=None):
+        """Enqueue the rate-constrained search of resident frames
+        (me_rd_search_device): ref_t / cur_t are uint8 tensors (H, pitch) or
+        batches [F, H, pitch], pred_t the quarter-pel predictors int16
+        [F * nblocks, 2] or None (all zero), mv_t int16 [F * nblocks, 2], cost_t
+        (J) and dist_t (SAD, or None) uint32/int32 [F * nblocks], bits_t uint8
+        [F * nblocks] or None.  width / height default to the tensors' last two
+        dimensions; the row pitch and the frame strides are the tensors'."""
+        self.prepared_rd_search(ref_t, cur_t, blk, span, lam, mv_t, cost_t, dist_t, bits_t, pred_t,
+                                cost, stream, width, height)()
+
+    def _plane_args(self, ref_t, cur_t, width, height):
+        if ref_t.dim() not in (2, 3) or ref_t.dim() != cur_t.dim() or \
+                ref_t.stride(-2) != cur_t.stride(-2) or \
+                (ref_t.dim() == 3 and ref_t.shape[0] != cur_t.shape[0]):
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {tuple(ref_t.shape)} / "
+                          f"{tuple(cur_t.shape)} or row pitches differ")
+        es = ref_t.element_size()
+        frames = ref_t.shape[0] if ref_t.dim() == 3 else 1
+        rfs = ref_t.stride(0) * es if ref_t.dim() == 3 else 0
+        cfs = cur_t.stride(0) * es if cur_t.dim() == 3 else 0
+        h = height if height else ref_t.shape[-2]
+        w = width if width else ref_t.shape[-1]
+        return frames, rfs, cfs, w, h, ref_t.stride(-2) * es
+
+    def prepared_rd_search(self, ref_t, cur_t, blk, span, lam, mv_t, cost_t, dist_t=None,
+                           bits_t=None, pred_t=None, cost="sad", stream=None, width=None,
+                           height=None):
+        """Zero-argument callable enqueueing rd_search_device(...) with these buffers."""
+        frames, rfs, cfs, w, h, pitch = self._plane_args(ref_t, cur_t, width, height)
+        opt = lambda t: t.data_ptr() if t is not None else None
+        fn, ctx = _lib.lib().me_rd_search_device, self._h
+        args = (ctx, ref_t.data_ptr(), rfs, cur_t.data_ptr(), cfs, w, h, pitch, blk, span,
+                cost_code(cost), lam, frames, opt(pred_t), opt(mv_t), opt(cost_t), opt(dist_t),
+                opt(bits_t), stream if stream is not None else _current_stream())
+
+        def run():
+            s = fn(*args)
+            if s:
+                check(s, ctx)
+        return run
+
+    def refine_qpel_rd_device(self, ref_t, cur_t, blk: int, cost, lam: int, mv_t, q_t=None,
+                              cost_t=None, dist_t=None, pred_t=None, stream=None, width=None,
+                              height=None):
+        """Enqueue the rate-constrained quarter-pel refinement of resident
+        frames (me_refine_qpel_rd_device): refine_qpel_device's arguments plus
+        lam, pred_t (int16 [F * nblocks, 2] or None: all zero) and dist_t (the
+        distortion at the result, or None); cost_t receives Jq."""
+        frames, rfs, cfs, w, h, pitch = self._plane_args(ref_t, cur_t, width, height)
+        opt = lambda t: t.data_ptr() if t is not None else None
+        check(_lib.lib().me_refine_qpel_rd_device(
+            self._h, ref_t.data_ptr(), rfs, cur_t.data_ptr(), cfs, w, h, pitch, blk,
+            cost_code(cost), lam, frames, opt(pred_t), mv_t.data_ptr(),
+            (q_t if q_t is not None else mv_t).data_ptr(), opt(cost_t), opt(dist_t),
+            stream if stream is not None else _current_stream()), self._h)
 
     def partition_leaf_field_device(self, width: int, height: int, blk: int, fields, leaf_t,
                                     frames: int = 1, stream=None):
