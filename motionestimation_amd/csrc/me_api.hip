@@ -81,6 +81,7 @@ static Tuning read_tuning() {
   env_int("ME_FLOW_ONE", 0, 1, &t.flow_one);
   env_int("ME_PRUNE", 0, 2, &t.prune);
   env_int("ME_PRUNE_BYPASS", 0, 1, &t.prune_bypass);
+  env_int("ME_PRUNE_PLANES", 0, 1, &t.prune_planes);
   t.prune_stats = 1;
   env_int("ME_MFMA_BATCH", 0, 1, &t.mfma_batch);
   env_int("ME_MFMA_S2K", 0, 1, &t.mfma_s2k);
@@ -222,7 +223,8 @@ me_status check_stripe(me_ctx* c, int nby, int blk, int range, int r0, int r1, i
   return fail(c, ME_EINVAL, "%scur_row0 %d", pre, cur_row0);
 }
 
-me_status attach_scratch(me_ctx* c, Dev& d, SearchArgs& p, bool cap, int batch) {
+me_status attach_scratch(me_ctx* c, Dev& d, SearchArgs& p, bool cap, int batch, const SearchJob* jobs,
+                         int njobs) {
   ME_CTX_PATH_SCOPE(c, d);  // the scratch follows the kernels the context's path plans
   p.sched = d.sched;
   {
@@ -251,6 +253,14 @@ me_status attach_scratch(me_ctx* c, Dev& d, SearchArgs& p, bool cap, int batch) 
   if (ssim > need) need = ssim;
   if (need && cap && (need > d.scratch_cap || !d.scratch))
     return fail(c, ME_EINVAL, "captured search needs new scratch: run it once uncaptured first");
+  // SAD on the pruning flow plan: the box-sum planes of every job of a launch.
+  // The search runs without them too, so a captured one takes the scratch as
+  // it is (launch_flow checks what it was lent).
+  if (p.cost_kind == me::COST_SAD) {
+    const SearchJob self{p.ref, p.ref_row0, p.cur, p.cur_row0, p.block_row_begin, p.block_row_end, p.mv, p.cost};
+    const size_t planes = me::flow_planes_need(p, jobs ? jobs : &self, jobs ? njobs : 1);
+    if (planes > need && !(cap && (planes > d.scratch_cap || !d.scratch))) need = planes;
+  }
   if (need) {
     me_status s = grow(c, (void**)&d.scratch, &d.scratch_cap, need);
     if (s != ME_OK) return s;
@@ -970,7 +980,7 @@ me_status me_search_stripes_device(me_ctx* c, int width, int height, int stride,
       same = same && jobs[i].block_row_begin == jobs[0].block_row_begin &&
              jobs[i].block_row_end == jobs[0].block_row_end && jobs[i].ref_row0 == jobs[0].ref_row0 &&
              jobs[i].cur_row0 == jobs[0].cur_row0;
-    me_status s = attach_scratch(c, d, base, cap, same ? n_jobs : 1);
+    me_status s = attach_scratch(c, d, base, cap, same ? n_jobs : 1, js.data(), n_jobs);
     if (s != ME_OK) return s;
   }
   c->err[0] = 0;

@@ -105,6 +105,11 @@ struct QsadGeom {
 // Bound scratch of one ring slot of the pruning flow kernel: four x-phase
 // planes of 77 rows x 32 box-sum bytes (the live list overlays them once the
 // bound is done), minlb[5][4][16] u32 and the cur blocks' 4 x 16 box-sum bytes.
+// Plane k, row r, byte i holds q of window position (r, 4 i + k), q = the 4x4
+// box sum >> 4.  The planes are filled one of two ways: by the staging wave's
+// LDS DMA from the job's box-sum planes in the context scratch (below; the
+// prepass me_box_planes_kernel wrote them once per reference plane), or, where
+// the launch has no such planes, by step 1 of flow_bound from the staged window.
 constexpr int FLOW_PRUNE_QROWS = 77;
 constexpr int FLOW_PRUNE_PLANE = FLOW_PRUNE_QROWS * 32;
 constexpr int FLOW_PRUNE_MINLB = 4 * FLOW_PRUNE_PLANE;
@@ -157,7 +162,31 @@ struct FlowJobs {
   const uint8_t* cur[MAX_JOBS];
   int16_t* mv[MAX_JOBS];
   uint32_t* cost[MAX_JOBS];
+  // The pruning flow launch's box-sum planes (null: the kernel forms the box
+  // sums itself): job j's at planes + 64 * plane_off64[j], plane_rows[j] rows
+  // (its resident ref rows, from ref_row0) of 4 x plane_pitch bytes.
+  uint8_t* planes;
+  int plane_pitch;
+  uint32_t plane_off64[MAX_JOBS];
+  int plane_rows[MAX_JOBS];
 };
+
+// ---- box-sum planes of the pruning flow plan (S = 32, 4-block tiles) ----
+// Per job, per resident ref row y (relative to ref_row0), four x-phase rows of
+// flow_plane_pitch bytes: row 4 y + k, byte i holds q(y, 4 i + k - 32).  The x
+// origin sits S = 32 pixels left of the frame, so the 32 bytes a tile at
+// X0 = 64 c - 32 needs start at byte 16 c of every phase row: 16-byte granules
+// for the LDS DMA.  Positions no valid candidate uses (x < 0, x > W - 4,
+// y > rows - 4) and the pitch padding hold 0.
+inline int flow_plane_pitch(int width) { return ((width + 64) / 4 + 15) & ~15; }
+// Resident ref rows of job J (ref_resident_bytes' rows).
+inline int flow_plane_rows(const SearchJob& J, int blk, int range, int height) {
+  const int end = J.r1 * blk + range < height ? J.r1 * blk + range : height;
+  return end > J.ref_row0 ? end - J.ref_row0 : 0;
+}
+inline size_t flow_plane_job_bytes(int width, int rows) {  // a multiple of 64
+  return (size_t)rows * 4 * (size_t)flow_plane_pitch(width);
+}
 
 // ---- the VALU kernels' planners (me_valu_plan.cpp: host-only, pure) ----
 
@@ -189,6 +218,16 @@ struct Tuning;  // me_tuning.h
 bool plan_fast(const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g, int* k_out);
 // The flow kernel's plan (me_flow_kernel<16, 13>); false: the item kernel's turn.
 bool plan_flow(const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g);
+// A pruning flow launch over njobs jobs reads its box sums from prepass planes
+// (tu.prune_planes, else the automatic rule).
+bool flow_planes_on(const Tuning& tu, int njobs);
+// Context scratch the SAD search of jobs [0, n) of s's frame needs for its
+// flow launches' box-sum planes (s.rows and s.align are not read: the plans
+// are made as the dispatcher makes them, over every job's rows and then job by
+// job): the largest sum of flow_plane_job_bytes over the jobs of one launch
+// (MAX_JOBS consecutive jobs at most).  0: no launch of it uses planes (not
+// SAD, no flow plan or one without pruning, planes off).
+size_t flow_planes_scratch(const PlanShape& s, int cus, const Tuning& tu, const SearchJob* jobs, int n);
 
 // Plans depend only on the shape: cached_plan keeps them (process-wide, one
 // ring of 8 per planner under a mutex: the per-device host threads share them)

@@ -151,8 +151,13 @@ me_status check_stripe(me_ctx* c, int nby, int blk, int range, int r0, int r1, i
 // cap: the launch is being captured (me_capture_begin): growing the scratch
 // then fails with ME_EINVAL (a graph must not hold buffers a later search frees).
 // batch > 1: scratch for that many equal-geometry jobs in shared launches
-// (mfma_batch_scratch), else for one search
-me_status attach_scratch(me_ctx* c, Dev& d, SearchArgs& p, bool cap = false, int batch = 1);
+// (mfma_batch_scratch), else for one search.
+// jobs [0, njobs): the job list p is the base of (any rows; null: p's own
+// search), for the box-sum planes of its SAD flow launches (flow_planes_need:
+// every job of a launch counts).  These are optional to the search: a captured
+// one that finds the scratch missing or smaller runs without them.
+me_status attach_scratch(me_ctx* c, Dev& d, SearchArgs& p, bool cap = false, int batch = 1,
+                         const SearchJob* jobs = nullptr, int njobs = 0);
 
 // Launch jobs [0, n) (launch_jobs: they share base's geometry, cost and
 // scratch; attach_scratch(base, cap, n) for equal jobs; one job for a single

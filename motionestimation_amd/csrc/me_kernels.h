@@ -60,6 +60,10 @@ __device__ __forceinline__ void store_mv(int16_t* mv, int out, unsigned long lon
 // dispatcher (me_dispatch.cpp) which kernel family takes which blocks and
 // walks its launch list.  A single search is a list of one job.
 hipError_t launch_jobs(const SearchArgs& base, const SearchJob* jobs, int n, hipStream_t stream);
+// Scratch bytes the flow launches of launch_jobs(base, jobs, n) want for their
+// box-sum planes (flow_planes_scratch, me_valu_plan.cpp, for this device and
+// tuning; 0: none).  A search lent less runs without planes.
+size_t flow_planes_need(const SearchArgs& base, const SearchJob* jobs, int n);
 
 // Matrix-core SSD path (me_mfma.hip, me_band.hip).  MfmaGeom, MfmaJobs and the
 // planners are in me_mfma_geom.h / me_mfma_plan.cpp (host-only, pure); the

@@ -947,7 +947,9 @@ struct FlowCtl {
   uint32_t live[16];   // live lane-tasks of the slot's item (its list's length)
   uint32_t stats[4];   // tuning build: live, all lane-tasks, bypassed items, items (flushed at the end)
 };
-enum { PF_ON = 1, PF_VERIFY = 2, PF_BYPASS = 4, PF_STATS = 8 };
+// PF_PLANES: the launch has box-sum planes (FlowJobs::planes): the staging wave
+// DMAs an item's four planes with its window, and flow_bound skips its step 1.
+enum { PF_ON = 1, PF_VERIFY = 2, PF_BYPASS = 4, PF_STATS = 8, PF_PLANES = 16 };
 static_assert(sizeof(FlowCtl) <= FLOW_CTL_BYTES, "control block of the pruning launch");
 
 // Tile of the flow kernel's launch -> its item (all dy chunks: one pass).
@@ -958,10 +960,19 @@ __device__ __forceinline__ Item flow_item(const SearchArgs& p, const QsadGeom& g
 }
 
 // Single-wave LDS DMA of one flow item (the aligned path): tile rows and cur
-// blocks, from its job's planes.
-template <int B>
-__device__ __forceinline__ void stage_item_wave(const SearchArgs& p, const QsadGeom& g, const Item& it,
-                                                uint8_t* buf, const FlowJobs& jb) {
+// blocks, from its job's planes.  PL (the pruning instance) and PF_PLANES set:
+// also the item's 4 x 77 rows x 32 bytes of box sums, from the job's box-sum
+// planes straight into the slot's bound scratch (the layout flow_bound's steps
+// 2-4 read), under the caller's one vmcnt wait.  Window rows outside the job's
+// resident rows are outside the plane buffer's range too: zeros, and masked
+// like the window's.  Not loaded for an item the bound will not look at (an
+// h = B/2 item; the bypass state).  Returns whether the planes were loaded:
+// the bypass state may end between here and the item's bound phase, which then
+// forms the box sums itself.  The plane base and the job's offset are read
+// here only (no SGPRs across the task loop).
+template <int B, bool PL>
+__device__ __forceinline__ bool stage_item_wave(const SearchArgs& p, const QsadGeom& g, const Item& it,
+                                                uint8_t* buf, const FlowJobs& jb, FlowCtl* ctl) {
   const __amdgpu_buffer_rsrc_t rref =
       __builtin_amdgcn_make_buffer_rsrc((void*)jb.ref[it.j], (short)0, jb.ref_bytes[it.j], 0x00020000);
   const __amdgpu_buffer_rsrc_t rcur =
@@ -990,6 +1001,31 @@ __device__ __forceinline__ void stage_item_wave(const SearchArgs& p, const QsadG
           rcur, (__attribute__((address_space(3))) void*)(cur + s0), 16,
           cbase + (uint32_t)(((d >> 4) & 15) * stride + (d >> 8) * B), 0, 0, 0);
   }
+  if constexpr (PL) {
+    const int pf = __builtin_amdgcn_readfirstlane((int)ctl->pflags);
+    if (!(pf & PF_PLANES) || it.h != B) return false;
+    if ((pf & PF_BYPASS) &&
+        __builtin_amdgcn_readfirstlane(
+            (int)__hip_atomic_load(&ctl->run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= 4)
+      return false;
+    const int pp = jb.plane_pitch;
+    const __amdgpu_buffer_rsrc_t rpl = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(jb.planes + ((size_t)jb.plane_off64[it.j] << 6)), (short)0, jb.plane_rows[it.j] * 4 * pp,
+        0x00020000);
+    uint8_t* pr = buf + g.tile_bytes + 4 * B * B;
+    // LDS byte d = plane k, row r, half hf  <-  phase row 4 (prow0 - ref_row0 + r) + k
+    const uint32_t pbase = (uint32_t)((it.prow0 - jb.ref_row0[it.j]) * 4 * pp + ((it.X0 + 32) >> 2));
+    for (int s0 = 0; s0 < 4 * FLOW_PRUNE_PLANE; s0 += 1024) {
+      const int d = s0 + 16 * lane;
+      const int k = d / FLOW_PRUNE_PLANE, rem = d - k * FLOW_PRUNE_PLANE;
+      if (d < 4 * FLOW_PRUNE_PLANE)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            rpl, (__attribute__((address_space(3))) void*)(pr + s0), 16,
+            pbase + (uint32_t)(((rem >> 5) * 4 + k) * pp + (rem & 16)), 0, 0, 0);
+    }
+    return true;
+  }
+  return false;
 }
 
 // Wave-tasks of one item: its lane-tasks (valid chunks x blocks x groups) / 64, rounded up.
@@ -1048,7 +1084,8 @@ __device__ __forceinline__ void lds_fence() {  // this wave's LDS writes before 
 
 template <int B, int K>
 __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& g, const Item& it,
-                                           uint8_t* buf, uint64_t* keys, FlowCtl* ctl, int slot) {
+                                           uint8_t* buf, uint64_t* keys, FlowCtl* ctl, int slot,
+                                           bool planes) {
   constexpr int S = 32, G = 16, TB = 4, P = 144;
   static_assert(B == 16 && K == 13, "bound scratch layout");
   const int lane = fresh_tid() & 63;
@@ -1106,8 +1143,10 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
   }
 
   // 1. box sums: the lane owns window columns x0, x0 + 1 and walks the 80 rows
-  // with a sliding 4-row sum of the packed horizontal 4-sums.
-  {
+  // with a sliding 4-row sum of the packed horizontal 4-sums.  (Not when the
+  // staging wave's DMA brought the planes: the same bytes wherever a valid
+  // candidate reads them.)
+  if (!planes) {
     const int x0 = 2 * lane, sh = x0 & 3;
     const uint8_t* src = buf + (x0 & ~3);
     uint8_t* dst = pr + sh * FLOW_PRUNE_PLANE + (x0 >> 2);  // planes sh and sh + 1
@@ -1126,6 +1165,8 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
         dst[(r - 3) * 32 + FLOW_PRUNE_PLANE] = (uint8_t)(v >> 20);
       }
     }
+  }
+  {
     // q of the cur blocks: lane = (block, sub-block row, sub-block column)
     const uint32_t* cw = cur + ((lane >> 4) * B + 4 * ((lane >> 2) & 3)) * 4 + (lane & 3);
     uint32_t sum = 0;
@@ -1328,7 +1369,7 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       ctl->run = 0;
       ctl->pflags = !prune ? 0u
                            : (uint32_t)(PF_ON | (g.prune == 2 ? PF_VERIFY : 0) | (g.prune_bypass ? PF_BYPASS : 0) |
-                                        (g.prune_stats ? PF_STATS : 0));
+                                        (g.prune_stats ? PF_STATS : 0) | (jb.planes ? PF_PLANES : 0));
     }
   }
   for (int i = tid; i < NB * g.tb; i += (int)blockDim.x) keys[i] = ~0ull;
@@ -1343,12 +1384,12 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     for (int i = 0; i < wave; i++) __builtin_amdgcn_s_sleep(10);
     if (g.prio) __builtin_amdgcn_s_setprio(3);  // see me_fast_kernel
     const Item it0 = flow_item<B, K>(p, g, jb, tile_of(wave));
-    stage_item_wave<B>(p, g, it0, smem + wave * slot_bytes, jb);
+    const bool pl0 = stage_item_wave<B, PC == 144>(p, g, it0, smem + wave * slot_bytes, jb, ctl);
     if (g.prio) __builtin_amdgcn_s_setprio(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if constexpr (PC == 144) {
       if (prune)
-        flow_bound<B, K>(p, g, it0, smem + wave * slot_bytes, keys + wave * g.tb, ctl, wave);
+        flow_bound<B, K>(p, g, it0, smem + wave * slot_bytes, keys + wave * g.tb, ctl, wave, pl0);
     }
     if (lane == 0)
       __hip_atomic_store(&ctl->ready[wave], (uint32_t)wave + 1u, __ATOMIC_RELEASE,
@@ -1556,7 +1597,7 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
 #ifdef ME_STAMPS
         const unsigned long long st_d0 = __builtin_amdgcn_s_memtime();
 #endif
-        stage_item_wave<B>(p, g, itn, buf, jb);
+        const bool pln = stage_item_wave<B, PC == 144>(p, g, itn, buf, jb, ctl);
         if (g.prio) __builtin_amdgcn_s_setprio(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #ifdef ME_STAMPS
@@ -1567,7 +1608,7 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
           // (at raised issue priority: nothing of the item runs before its bound ends)
           if (pfl) {
             __builtin_amdgcn_s_setprio(3);
-            flow_bound<B, K>(p, g, itn, buf, keys + slot * g.tb, ctl, slot);
+            flow_bound<B, K>(p, g, itn, buf, keys + slot * g.tb, ctl, slot, pln);
             __builtin_amdgcn_s_setprio(0);
           }
         }
@@ -1600,6 +1641,95 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     }
   }
 #endif
+}
+
+// ------------------------------------------------- flow: the box-sum prepass
+// q = (4x4 box sum) >> 4 of every job's resident reference rows, once per
+// launch, as the x-phase planes of me_geom.h (flow_plane_pitch): the flow
+// kernel's bound phase would otherwise form the same sums in every tile whose
+// window holds the pixel, about ten times per frame.  Memory bound: a thread
+// owns 16 consecutive x (one dword of each phase row: a wave stores 256
+// contiguous bytes per phase) and PLANES_RPT rows, reading each of its
+// PLANES_RPT + 3 input rows once as one 16-byte and one 4-byte load and
+// keeping the last three rows' packed horizontal 4-sums (four v_qsad_pk_u16_u8
+// per row and v_perm_b32 to sort the bytes by phase: 16.8 us per 16 1080p
+// frames, 66 MB moved; with v_alignbyte + v_sad_u8 per x it took 21.2 us).
+constexpr int PLANES_RPT = 8;
+__global__ __launch_bounds__(256) void me_box_planes_kernel(FlowJobs jb, int width, int stride) {
+  const int j = (int)blockIdx.z;
+  const int pitch = jb.plane_pitch, rows = jb.plane_rows[j];
+  const int t = (int)(blockIdx.x * 64 + threadIdx.x);  // dword of a phase row
+  const int y0 = (int)(blockIdx.y * 4 + threadIdx.y) * PLANES_RPT;
+  if (4 * t >= pitch || y0 >= rows) return;
+  const int xb = 16 * t - 32;  // the thread's first x
+  const bool inx = xb >= 0 && xb < width;  // (W % 16 == 0: all 16 inside or none)
+  const uint8_t* src = jb.ref[j] + xb;
+  uint8_t* dst = jb.planes + ((size_t)jb.plane_off64[j] << 6) + 4 * t;
+  // Bytes of the thread's phase dwords that hold a valid x (<= W - 4): all of
+  // them, but for the frame's last 16 columns (x = W - 3 .. W - 1 are out).
+  uint32_t keep[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    keep[k] = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      if (inx && xb + 4 * i + k <= width - 4) keep[k] |= 0xFFu << (8 * i);
+  }
+  // h[g]: the row's four horizontal 4-sums at x = 4 g .. 4 g + 3 as packed u16
+  // (one v_qsad_pk_u16_u8 against zero), lo = x, x + 1; hi = x + 2, x + 3.
+  uint32_t h1l[4], h1h[4], h2l[4], h2h[4], h3l[4], h3h[4];
+#pragma unroll
+  for (int g = 0; g < 4; g++) h1l[g] = h1h[g] = h2l[g] = h2h[g] = h3l[g] = h3h[g] = 0;
+#pragma unroll
+  for (int r = 0; r < PLANES_RPT + 3; r++) {
+    const int y = y0 + r;
+    uint32_t w[5] = {0, 0, 0, 0, 0};
+    if (inx && y < rows) {
+      const uint4 v = *reinterpret_cast<const uint4*>(src + (size_t)y * stride);
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+      if (xb + 16 < width) w[4] = *reinterpret_cast<const uint32_t*>(src + (size_t)y * stride + 16);
+    }
+    uint32_t h0l[4], h0h[4];
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+      const uint64_t h = __builtin_amdgcn_qsad_pk_u16_u8(((uint64_t)w[g + 1] << 32) | w[g], 0u, 0ull);
+      h0l[g] = (uint32_t)h;
+      h0h[g] = (uint32_t)(h >> 32);
+    }
+    if (r >= 3) {
+      const int yo = y - 3;  // the box's top row; its bottom row y is resident or q is 0
+      if (yo < rows) {
+        // q pairs: four row sums <= 1020 each, no carry between the u16 halves
+        uint32_t ql[4], qh[4];
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+          ql[g] = ((h0l[g] + h1l[g] + h2l[g] + h3l[g]) >> 4) & 0x00FF00FFu;  // q(4g) | q(4g + 1) << 16
+          qh[g] = ((h0h[g] + h1h[g] + h2h[g] + h3h[g]) >> 4) & 0x00FF00FFu;  // q(4g + 2) | q(4g + 3) << 16
+        }
+        // phase k's dword = q(k), q(4 + k), q(8 + k), q(12 + k): byte 0 (k even)
+        // or 2 (k odd) of the four groups' pairs (v_perm_b32: selector bytes 0-3
+        // take the second operand's bytes, 4-7 the first's)
+        const uint32_t l01 = __builtin_amdgcn_perm(ql[1], ql[0], 0x06020400u);
+        const uint32_t l23 = __builtin_amdgcn_perm(ql[3], ql[2], 0x06020400u);
+        const uint32_t u01 = __builtin_amdgcn_perm(qh[1], qh[0], 0x06020400u);
+        const uint32_t u23 = __builtin_amdgcn_perm(qh[3], qh[2], 0x06020400u);
+        uint32_t o[4];
+        o[0] = __builtin_amdgcn_perm(l23, l01, 0x05040100u);
+        o[1] = __builtin_amdgcn_perm(l23, l01, 0x07060302u);
+        o[2] = __builtin_amdgcn_perm(u23, u01, 0x05040100u);
+        o[3] = __builtin_amdgcn_perm(u23, u01, 0x07060302u);
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          *reinterpret_cast<uint32_t*>(dst + ((size_t)yo * 4 + k) * pitch) = y < rows ? o[k] & keep[k] : 0u;
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+      h3l[g] = h2l[g]; h3h[g] = h2h[g];
+      h2l[g] = h1l[g]; h2h[g] = h1h[g];
+      h1l[g] = h0l[g]; h1h[g] = h0h[g];
+    }
+  }
 }
 
 // ------------------------------------------------------------------ launch
@@ -1735,6 +1865,8 @@ static FlowJobs job_table(const SearchArgs& p, int wg_per_row, const SearchJob* 
   FlowJobs jb;
   jb.n = 0;
   jb.tile_pre[0] = 0;
+  jb.planes = nullptr;  // (launch_flow binds the box-sum planes)
+  jb.plane_pitch = 0;
   for (int i = 0; i < n; i++) {
     const SearchJob& J = jobs[i];
     if (J.r1 <= J.r0) continue;
@@ -1749,6 +1881,8 @@ static FlowJobs job_table(const SearchArgs& p, int wg_per_row, const SearchJob* 
     jb.cur[j] = J.cur;
     jb.mv[j] = J.mv;
     jb.cost[j] = J.cost;
+    jb.plane_off64[j] = 0;
+    jb.plane_rows[j] = flow_plane_rows(J, p.blk, p.range, p.height);
     jb.tile_pre[j + 1] = jb.tile_pre[j] + wg_per_row * (J.r1 - J.r0);
   }
   return jb;
@@ -1758,10 +1892,35 @@ static FlowJobs job_table(const SearchArgs& p, int wg_per_row, const SearchJob* 
 // bottom rows only; n <= MAX_JOBS).
 static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const SearchJob* jobs, int n,
                               hipStream_t stream) {
-  const FlowJobs jb = job_table(p, g.wg_per_row, jobs, n);
+  FlowJobs jb = job_table(p, g.wg_per_row, jobs, n);
   const int ntiles = jb.tile_pre[jb.n];
   if (ntiles <= 0) return hipSuccess;
   const int nwg = ntiles > cu_count() ? cu_count() : ntiles;  // one per CU, at most one per tile
+  // The pruning launch's box-sum planes, in the scratch the context lent the
+  // search when it holds every job's (attach_scratch sized it with
+  // flow_planes_need; a captured search that met a smaller one runs without):
+  // the prepass goes in front on the same stream.
+  if (g.pitch == 144 && g.prune && p.scratch && flow_planes_on(tuning(), jb.n)) {
+    size_t off = 0;
+    int max_rows = 0;
+    bool ok = true;
+    for (int j = 0; j < jb.n; j++) {
+      const size_t b = flow_plane_job_bytes(p.width, jb.plane_rows[j]);
+      jb.plane_off64[j] = (uint32_t)(off >> 6);
+      off += b;
+      ok = ok && b > 0 && b < (1u << 31);
+      if (jb.plane_rows[j] > max_rows) max_rows = jb.plane_rows[j];
+    }
+    if (ok && off <= p.scratch_bytes) {
+      jb.planes = p.scratch;
+      jb.plane_pitch = flow_plane_pitch(p.width);
+      const dim3 grid((unsigned)((jb.plane_pitch / 4 + 63) / 64),
+                      (unsigned)((max_rows + 4 * PLANES_RPT - 1) / (4 * PLANES_RPT)), (unsigned)jb.n);
+      hipLaunchKernelGGL(me_box_planes_kernel, grid, dim3(64, 4), 0, stream, jb, p.width, p.stride);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+  }
   // 144: the pitch of the 4-block tiles 1080p +-32 gets (row addresses in
   // the ds_read2 offsets); any other pitch takes the runtime-pitch body
 #define ME_FLOW_CASE(PP)                                                                        \
@@ -1776,6 +1935,11 @@ static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const Sear
   ME_FLOW_CASE(144) ME_FLOW_CASE(0)
 #undef ME_FLOW_CASE
   return hipErrorInvalidValue;
+}
+
+size_t flow_planes_need(const SearchArgs& base, const SearchJob* jobs, int n) {
+  const PlanShape s{base.width, base.height, base.stride, base.blk, base.range, base.cost_kind, 0, 0};
+  return flow_planes_scratch(s, cu_count(), tuning(), jobs, n);
 }
 
 size_t merge_tiles_needed(const SearchArgs& p) {

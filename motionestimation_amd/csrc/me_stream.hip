@@ -469,7 +469,7 @@ me_status run_pairs(me_ctx* c, Dev& d, const Job& j, int p0, int p1) {
       else if (q != hipSuccess)
         return fail(c, ME_EDEVICE, "upload event: %s", hipGetErrorString(q));
     }
-    if ((s = me::attach_scratch(c, d, base, false, n1 - n0)) != ME_OK) return s;
+    if ((s = me::attach_scratch(c, d, base, false, n1 - n0, jobs.data(), n1 - n0)) != ME_OK) return s;
     if ((s = me::launch_ordered(c, d, base, jobs.data(), n1 - n0, d.stream)) != ME_OK) return s;
     HIPCHK(c, hipEventRecord(d.batch_ev[batch % kEvRing], d.stream));
     ranges.emplace_back(n0, n1);

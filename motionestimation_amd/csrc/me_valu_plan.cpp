@@ -427,4 +427,52 @@ bool cached_plan(PlanKind kind, const PlanShape& s, int cus, const Tuning& tu, Q
   return hit->ok;
 }
 
+// Automatic: launches of two or more jobs.  A launch of one job pays a whole
+// extra kernel launch for one frame's planes and has few refills to win it
+// back on: one 1080p frame measured 68.1-68.9 us with the planes against
+// 68.7-69.4 without, overlapping (profiles/planes_single_frame_ab.jsonl; 70.5-
+// 71.3 against 69.1-69.6 with the first, slower prepass), so it keeps the
+// parent's launch.  Two frames: 107.1-107.6 against 111.0-111.1 us; four:
+// 179.0-179.6 against 189.0-189.7; the 16-frame batch 0.643-0.645 ms against
+// 0.690-0.693 (profiles/planes_frames{2,4}_ab.jsonl, planes_bench_ab.txt).
+bool flow_planes_on(const Tuning& tu, int njobs) {
+  if (tu.prune_planes >= 0) return tu.prune_planes != 0;
+  return njobs >= 2;
+}
+
+size_t flow_planes_scratch(const PlanShape& s, int cus, const Tuning& tu, const SearchJob* jobs, int n) {
+  if (s.cost != COST_SAD || n < 1) return 0;
+  // jobs [j0, j0 + m) as the dispatcher's flow_jobs plans them
+  auto need = [&](int j0, int m) -> size_t {
+    if (!flow_planes_on(tu, m < MAX_JOBS ? m : MAX_JOBS)) return 0;
+    PlanShape ps = s;
+    ps.rows = 0;
+    ps.align = align_class(s.stride, jobs[j0].ref, jobs[j0].cur);
+    for (int i = j0; i < j0 + m; i++) {
+      ps.rows += jobs[i].r1 - jobs[i].r0;
+      if ((uintptr_t)jobs[i].ref % 16 || (uintptr_t)jobs[i].cur % 16) return 0;
+    }
+    QsadGeom g;
+    if (!cached_plan(PLAN_FLOW, ps, cus, tu, &g, nullptr) || !g.prune) return 0;
+    size_t best = 0, sum = 0;  // the largest window of MAX_JOBS consecutive jobs
+    for (int i = j0; i < j0 + m; i++) {
+      sum += flow_plane_job_bytes(s.width, flow_plane_rows(jobs[i], s.blk, s.range, s.height));
+      if (i - j0 >= MAX_JOBS)
+        sum -= flow_plane_job_bytes(s.width, flow_plane_rows(jobs[i - MAX_JOBS], s.blk, s.range, s.height));
+      if (sum > best) best = sum;
+    }
+    return best;
+  };
+  if (n >= 2) {
+    const size_t b = need(0, n);
+    if (b) return b;
+  }
+  size_t best = 0;
+  for (int j = 0; j < n; j++) {
+    const size_t b = jobs[j].r1 > jobs[j].r0 ? need(j, 1) : 0;
+    if (b > best) best = b;
+  }
+  return best;
+}
+
 }  // namespace me

@@ -1,7 +1,14 @@
 # Native tools: the C host driver (reference argv, GPU search) and the VALU microbenchmark.
 HIPCC ?= /opt/rocm/bin/hipcc
 CC    ?= gcc
-all: bin/mes_hip bin/mes_seq bin/valu_microbench
+CXX   ?= g++
+all: bin/mes_hip bin/mes_seq bin/valu_microbench bin/flow_planes_dump
+
+# CPU harness of the box-sum planes' scratch sizing (the planner file alone)
+CSRC = motionestimation_amd/csrc
+bin/flow_planes_dump: tools/flow_planes_dump.cc $(CSRC)/me_valu_plan.cpp $(CSRC)/me_geom.h $(CSRC)/me_tuning.h
+	mkdir -p bin
+	$(CXX) -O1 -std=c++17 -Wall -I$(CSRC) -o $@ tools/flow_planes_dump.cc $(CSRC)/me_valu_plan.cpp -lpthread
 
 bin/mes_hip: tools/mes_main.c include/me.h motionestimation_amd/lib/libme_hip.so
 	mkdir -p bin
