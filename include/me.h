@@ -707,6 +707,95 @@ me_status me_full_search_rd_qpel(me_ctx* ctx, const uint8_t* ref, const uint8_t*
                                  me_cost cost, uint32_t lambda, const int16_t* pred_q,
                                  int16_t* mv_q, uint32_t* block_cost);
 
+/* ---- rate-constrained partition search: J per partition, mode by rate ----
+ * The partition search with the cost of coding each vector in the objective
+ * and the mode priced by its code length.  No reference counterpart; parity is
+ * against the numpy restatement tests/partition_rd_ref.py.  Grids, partitions,
+ * candidate displacements, storage order and the leaf field are those of
+ * "partition search" above, unchanged; bits(v) and the quarter-pel predictor
+ * units are those of "rate-constrained motion search".  On top of them (exact
+ * integers; DESIGN.md "Rate-constrained partition search"):
+ *   - predictor: one int16 (px, py) per macroblock in quarter-pel units,
+ *     pred_q[nby][nbx][2], the layout of me_rd_search's predictor at block size
+ *     B, so one array feeds both calls.  NULL means all zero; any int16 value
+ *     is legal.  All nine partitions of a macroblock use the macroblock's
+ *     predictor: it is what an encoder knows before it has chosen the shape.
+ *   - rate and cost: the rate of displacement d = (dx, dy) of macroblock b is
+ *     R_b(d) = bits(4 dx - px) + bits(4 dy - py) <= 66; the cost of partition p
+ *     of b at d is J_p(d) = SAD_p(d) + lambda * R_b(d).
+ *   - winner per partition: the first minimum of J_p in raster order of the
+ *     displacements (dy outer, dx inner, strict <).  Per cell of each grid: the
+ *     vector, cost = J_p, dist = SAD_p and bits = R (one byte).
+ *   - mode: J(m) = sum of J_p over the non-empty partitions of shape m +
+ *     lambda * mbits(m), mbits = (1, 3, 3, 5), the ue(m) code lengths.  Modes
+ *     are tried in the order 0, 1, 2, 3 and a later one replaces the best only
+ *     if strictly smaller.  mode: one byte; mode_cost: J(mode) as u32.
+ *   - limits: lambda <= ME_PART_RD_MAX_LAMBDA, which keeps J below 2^32 at
+ *     B = 32 (261,120 + (4 * 66 + 5) * 2^23 < 2^32); a larger lambda returns
+ *     ME_EINVAL.  Every other limit is me_partition_search's: B in {8, 16, 32}
+ *     and S <= ME_PART_MAX_RANGE, SAD only, whole frames on the context's
+ *     first device only (several devices or repeated ids: ME_EUNSUPPORTED),
+ *     stride * height < 2^31.
+ *   - identities: (E1) with lambda = 0 the four vector fields, their costs,
+ *     mode and mode_cost are me_partition_search's at lambda = 0 bit for bit,
+ *     whatever the predictor, and dist == cost.  (E2) The 2Nx2N records
+ *     (vector, J, dist, bits) are me_rd_search's at (B, S, lambda, the same
+ *     predictor) bit for bit, for every B.  (E3) The NxN records of a full-size
+ *     macroblock whose window is clamped on no side are me_rd_search's at
+ *     (B/2, S, lambda) with each macroblock's predictor repeated over its four
+ *     quarters.  (E4) For lambda1 < lambda2 and every cell, bits1 >= bits2 and
+ *     dist1 <= dist2.  (E5) With the leaf field compensated by
+ *     me_compensate_planes at B/2, sum |mc - cur| = sum over the macroblocks of
+ *     the dist_p of the chosen mode's partitions = sum of (mode_cost - lambda *
+ *     (mbits(mode) + sum of bits_p)). */
+#define ME_PART_RD_MAX_LAMBDA (1u << 23)
+
+/* The records of a rate-constrained partition search: f as in me_part_fields
+ * (cost_* = J_p; mv_* and mode required, the rest optional), plus the
+ * distortion and the rate of every cell, laid out like the cost_* arrays. */
+typedef struct me_part_rd_fields {
+  me_part_fields f;
+  uint32_t* dist_2nx2n; /* each may be NULL */
+  uint32_t* dist_2nxn;
+  uint32_t* dist_nx2n;
+  uint32_t* dist_nxn;
+  uint8_t* bits_2nx2n;  /* each may be NULL */
+  uint8_t* bits_2nxn;
+  uint8_t* bits_nx2n;
+  uint8_t* bits_nxn;
+} me_part_rd_fields;
+
+/* The kernel that takes the frame's full-size macroblocks: ME_PART_KERNEL_FAST
+ * where me_partition_kernel_variant says so and lambda <= ME_RD_FAST_MAX_LAMBDA
+ * (the fast kernel's 32-bit lane key J << 6 | index needs 65,280 + 66 lambda <
+ * 2^26, as in me_rd_kernel_variant), else ME_PART_KERNEL_GENERIC; -1 for
+ * arguments the search rejects.  Host only; the launch consults this same
+ * function (and checks the planes' and frame strides' 4-byte alignment on
+ * top). */
+int me_partition_rd_kernel_variant(int width, int height, int stride, int block_size,
+                                   int search_range, uint32_t lambda);
+
+/* Search n_frames >= 1 whole frames of one geometry on HBM-resident planes of
+ * ctx's first device, laid out as for me_partition_search_device; frame f's
+ * predictors at d_pred_q + 2 * f * nbx * nby (NULL: all zero).  d_out is a HOST
+ * struct of device pointers, read before the call returns.  Asynchronous on
+ * `stream`, ordered after the context's previous search like any search; uses
+ * no context scratch, so it can be captured (me_capture_begin) without a
+ * warm-up call.  me_partition_leaf_field* take &d_out->f as they are. */
+me_status me_partition_rd_search_device(me_ctx* ctx, const uint8_t* d_ref,
+                                        size_t ref_frame_stride, const uint8_t* d_cur,
+                                        size_t cur_frame_stride, int width, int height,
+                                        int stride, int block_size, int search_range,
+                                        me_cost cost, uint32_t lambda, int n_frames,
+                                        const int16_t* d_pred_q, const me_part_rd_fields* d_out,
+                                        void* stream);
+
+/* The same on host planes of row pitch `stride` and host arrays, synchronous. */
+me_status me_partition_rd_search(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int width,
+                                 int height, int stride, int block_size, int search_range,
+                                 me_cost cost, uint32_t lambda, const int16_t* pred_q,
+                                 const me_part_rd_fields* out);
+
 /* ---- frame-pair streaming ---- */
 
 /* Pinned (page-locked) host memory.  Frames that live in it are DMAed

@@ -33,6 +33,7 @@ ME_PART_KERNEL_GENERIC, ME_PART_KERNEL_FAST = 0, 1  # me_partition_kernel_varian
 ME_RD_MAX_RANGE, ME_RD_MAX_LAMBDA = 128, 1 << 24  # rate-constrained search
 ME_RD_FAST_MAX_LAMBDA = 1015811  # the fast kernel's largest lambda
 ME_RD_KERNEL_GENERIC, ME_RD_KERNEL_FAST = 0, 1  # me_rd_kernel_variant
+ME_PART_RD_MAX_LAMBDA = 1 << 23  # rate-constrained partition search
 
 # Every symbol include/me.h declares, with (restype, argtypes).
 _u8p = ctypes.c_void_p
@@ -144,6 +145,13 @@ _SIGS = {
                           [ctypes.c_uint32] + [ctypes.c_void_p] * 5),
     "me_full_search_rd_qpel": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] + [ctypes.c_int] * 6 +
                                [ctypes.c_uint32] + [ctypes.c_void_p] * 3),
+    "me_partition_rd_kernel_variant": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_uint32]),
+    # (the me_part_rd_fields arguments are ctypes.byref(engine.PartRdFields))
+    "me_partition_rd_search_device": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_size_t, _u8p,
+                                                     ctypes.c_size_t] + [ctypes.c_int] * 6 +
+                                      [ctypes.c_uint32, ctypes.c_int] + [ctypes.c_void_p] * 3),
+    "me_partition_rd_search": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] + [ctypes.c_int] * 6 +
+                               [ctypes.c_uint32] + [ctypes.c_void_p] * 2),
     "me_mv_read_header": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
     "me_mv_read": (ctypes.c_int, [ctypes.c_char_p] + [ctypes.c_void_p] * 4),
 }

@@ -815,11 +815,13 @@ extern "C" int me_debug_prune_stats(me_ctx* c, uint32_t* out4) {
 }
 #endif
 
-// A captured step: the graph plus what its searches point into.
+// A captured step: the graph plus what its searches point into (the sizes
+// too: a regrown buffer can come back at the address of the one it replaced).
 struct me_graph {
   me_ctx* ctx;
   hipGraphExec_t exec;
   const void *sched, *scratch, *mkeys, *mcnt;
+  size_t scratch_cap, merge_cap;
 };
 
 me_status me_capture_begin(me_ctx* c, void* stream) {
@@ -841,7 +843,8 @@ me_status me_capture_end(me_ctx* c, void* stream, me_graph** out) {
   (void)hipGraphDestroy(g);
   HIPCHK(c, e);
   const Dev& d = c->devs[0];
-  me_graph* gr = new (std::nothrow) me_graph{c, ex, d.sched, d.scratch, d.mkeys, d.mcnt};
+  me_graph* gr = new (std::nothrow) me_graph{c, ex, d.sched, d.scratch, d.mkeys, d.mcnt,
+                                               d.scratch_cap, d.merge_cap};
   if (!gr) {
     (void)hipGraphExecDestroy(ex);
     return fail(c, ME_ENOMEM, "graph");
@@ -854,7 +857,8 @@ me_status me_graph_launch(me_graph* g, void* stream) {
   if (!g) return ME_EINVAL;
   me_ctx* c = g->ctx;
   Dev& d = c->devs[0];
-  if (d.sched != g->sched || d.scratch != g->scratch || d.mkeys != g->mkeys || d.mcnt != g->mcnt)
+  if (d.sched != g->sched || d.scratch != g->scratch || d.mkeys != g->mkeys || d.mcnt != g->mcnt ||
+      d.scratch_cap != g->scratch_cap || d.merge_cap != g->merge_cap)
     return fail(c, ME_EINVAL, "the context's search scratch was regrown after capture: capture again");
   me_status s = me::order_on(c, d, (hipStream_t)stream);
   if (s != ME_OK) return s;
@@ -1839,6 +1843,125 @@ me_status me_full_search_rd_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* c
   HIPCHK(c, hipMemcpyAsync(mv_q, r.mv, nb * 4, hipMemcpyDeviceToHost, d.stream));
   if (block_cost)
     HIPCHK(c, hipMemcpyAsync(block_cost, r.cost, nb * 4, hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(c, hipStreamSynchronize(d.stream));
+  return ME_OK;
+}
+
+// ---- rate-constrained partition search (me_partition_rd.hip) ----
+
+// me_partition_search's argument rules with this search's lambda limit.
+static me_status check_partition_rd(me_ctx* c, const void* ref, const void* cur, int width,
+                                    int height, int stride, int blk, int range, me_cost cost,
+                                    uint32_t lambda, const me_part_rd_fields* out, int n[4]) {
+  if (!c) return ME_EINVAL;
+  if (!out) return fail(c, ME_EINVAL, "null plane or field pointer");
+  const me_status s = check_partition(c, ref, cur, width, height, stride, blk, range, cost, 0,
+                                      &out->f, n);
+  if (s != ME_OK) return s;
+  if (lambda > ME_PART_RD_MAX_LAMBDA)
+    return fail(c, ME_EINVAL, "lambda %u above ME_PART_RD_MAX_LAMBDA", lambda);
+  return ME_OK;
+}
+
+// Enqueue the search of n_frames frames on s after the device's previous
+// search (not while capturing: me_graph_launch orders the graph).
+static me_status partition_rd_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rfs,
+                                 const uint8_t* d_cur, size_t cfs, int width, int height,
+                                 int stride, int blk, int range, uint32_t lambda, int n_frames,
+                                 const int16_t* d_pred, const me_part_rd_fields& out,
+                                 hipStream_t s) {
+  if (!me::capturing(s)) {
+    me_status st = me::order_on(c, d, s);
+    if (st != ME_OK) return st;
+  }
+  // the kernel me_partition_rd_kernel_variant names; its LDS DMA also needs
+  // planes and frame strides that are multiples of 4 bytes
+  const bool fast = me_partition_rd_kernel_variant(width, height, stride, blk, range, lambda) ==
+                        ME_PART_KERNEL_FAST &&
+                    ((uintptr_t)d_ref | (uintptr_t)d_cur | (n_frames > 1 ? rfs | cfs : 0)) % 4 == 0;
+  const hipError_t e = me::launch_partition_rd_search(d_ref, rfs, d_cur, cfs, width, height,
+                                                      stride, blk, range, lambda, n_frames, fast,
+                                                      d_pred, out, s);
+  if (e != hipSuccess)
+    return me::fail(c, ME_EDEVICE, "rate-constrained partition search launch: %s",
+                    hipGetErrorString(e));
+  return ME_OK;
+}
+
+me_status me_partition_rd_search_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
+                                        const uint8_t* d_cur, size_t cur_frame_stride, int width,
+                                        int height, int stride, int blk, int range, me_cost cost,
+                                        uint32_t lambda, int n_frames, const int16_t* d_pred_q,
+                                        const me_part_rd_fields* d_out, void* stream) {
+  if (!c) return ME_EINVAL;
+  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
+  int n[4];
+  me_status s = check_partition_rd(c, d_ref, d_cur, width, height, stride, blk, range, cost,
+                                   lambda, d_out, n);
+  if (s != ME_OK) return s;
+  if ((s = check_frame_strides(c, stride, height, n_frames, ref_frame_stride,
+                               cur_frame_stride)) != ME_OK)
+    return s;
+  c->err[0] = 0;
+  return partition_rd_on(c, c->devs[0], d_ref, ref_frame_stride, d_cur, cur_frame_stride, width,
+                         height, stride, blk, range, lambda, n_frames, d_pred_q, *d_out,
+                         (hipStream_t)stream);
+}
+
+me_status me_partition_rd_search(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
+                                 int height, int stride, int blk, int range, me_cost cost,
+                                 uint32_t lambda, const int16_t* pred_q,
+                                 const me_part_rd_fields* out) {
+  int n[4];
+  me_status s = check_partition_rd(c, ref, cur, width, height, stride, blk, range, cost, lambda,
+                                   out, n);
+  if (s != ME_OK) return s;
+  c->err[0] = 0;
+  Dev& d = c->devs[0];
+  // records in d.rec: the predictors, the four vector, cost and distortion
+  // fields and the mode costs (4 bytes per cell each), then the four rate
+  // fields and the mode bytes
+  const size_t cells = (size_t)n[0] + n[1] + n[2] + n[3];
+  const size_t bytes = 4 * (size_t)n[0] + 12 * cells + 4 * (size_t)n[0] + cells + (size_t)n[0];
+  if ((s = upload_pair(c, d, ref, cur, width, height, stride, (bytes + 7) / 8)) != ME_OK) return s;
+  me_part_rd_fields D;
+  uint8_t* p = d.rec;
+  int16_t* d_pred = nullptr;
+  if (pred_q) {
+    d_pred = reinterpret_cast<int16_t*>(p);
+    HIPCHK(c, hipMemcpyAsync(d_pred, pred_q, 4 * (size_t)n[0], hipMemcpyHostToDevice, d.stream));
+  }
+  p += 4 * (size_t)n[0];
+  int16_t** mv[4] = {&D.f.mv_2nx2n, &D.f.mv_2nxn, &D.f.mv_nx2n, &D.f.mv_nxn};
+  uint32_t** co[4] = {&D.f.cost_2nx2n, &D.f.cost_2nxn, &D.f.cost_nx2n, &D.f.cost_nxn};
+  uint32_t** di[4] = {&D.dist_2nx2n, &D.dist_2nxn, &D.dist_nx2n, &D.dist_nxn};
+  uint8_t** bi[4] = {&D.bits_2nx2n, &D.bits_2nxn, &D.bits_nx2n, &D.bits_nxn};
+  for (int g = 0; g < 4; g++) *mv[g] = reinterpret_cast<int16_t*>(p), p += 4 * (size_t)n[g];
+  for (int g = 0; g < 4; g++) *co[g] = reinterpret_cast<uint32_t*>(p), p += 4 * (size_t)n[g];
+  for (int g = 0; g < 4; g++) *di[g] = reinterpret_cast<uint32_t*>(p), p += 4 * (size_t)n[g];
+  D.f.mode_cost = reinterpret_cast<uint32_t*>(p), p += 4 * (size_t)n[0];
+  for (int g = 0; g < 4; g++) *bi[g] = p, p += (size_t)n[g];
+  D.f.mode = p;
+  if ((s = partition_rd_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, range, lambda, 1,
+                           d_pred, D, d.stream)) != ME_OK)
+    return s;
+  int16_t* const hmv[4] = {out->f.mv_2nx2n, out->f.mv_2nxn, out->f.mv_nx2n, out->f.mv_nxn};
+  uint32_t* const hco[4] = {out->f.cost_2nx2n, out->f.cost_2nxn, out->f.cost_nx2n,
+                            out->f.cost_nxn};
+  uint32_t* const hdi[4] = {out->dist_2nx2n, out->dist_2nxn, out->dist_nx2n, out->dist_nxn};
+  uint8_t* const hbi[4] = {out->bits_2nx2n, out->bits_2nxn, out->bits_nx2n, out->bits_nxn};
+  for (int g = 0; g < 4; g++) {
+    const size_t b4 = 4 * (size_t)n[g];
+    HIPCHK(c, hipMemcpyAsync(hmv[g], *mv[g], b4, hipMemcpyDeviceToHost, d.stream));
+    if (hco[g]) HIPCHK(c, hipMemcpyAsync(hco[g], *co[g], b4, hipMemcpyDeviceToHost, d.stream));
+    if (hdi[g]) HIPCHK(c, hipMemcpyAsync(hdi[g], *di[g], b4, hipMemcpyDeviceToHost, d.stream));
+    if (hbi[g])
+      HIPCHK(c, hipMemcpyAsync(hbi[g], *bi[g], (size_t)n[g], hipMemcpyDeviceToHost, d.stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(out->f.mode, D.f.mode, (size_t)n[0], hipMemcpyDeviceToHost, d.stream));
+  if (out->f.mode_cost)
+    HIPCHK(c, hipMemcpyAsync(out->f.mode_cost, D.f.mode_cost, 4 * (size_t)n[0],
+                             hipMemcpyDeviceToHost, d.stream));
   HIPCHK(c, hipStreamSynchronize(d.stream));
   return ME_OK;
 }

@@ -150,6 +150,14 @@ hipError_t launch_rd_search(const uint8_t* ref, size_t ref_frame_stride, const u
                             int range, uint32_t lambda, int n_frames, bool fast,
                             const int16_t* pred, int16_t* mv, uint32_t* cost, uint32_t* dist,
                             uint8_t* bits, hipStream_t stream);
+// Rate-constrained partition search (me_partition_rd.hip): launch_partition_search
+// on J_p = SAD_p + lambda * bits(4 d - pred), pred [n_frames][nby][nbx][2]
+// quarter-pel or null (all zero); fast: me_partition_rd_kernel_variant's answer.
+hipError_t launch_partition_rd_search(const uint8_t* ref, size_t ref_frame_stride,
+                                      const uint8_t* cur, size_t cur_frame_stride, int width,
+                                      int height, int stride, int blk, int range, uint32_t lambda,
+                                      int n_frames, bool fast, const int16_t* pred,
+                                      const me_part_rd_fields& out, hipStream_t stream);
 // launch_compensate with quarter-pel vectors and edge-replicated samples.
 hipError_t launch_qpel_compensate(const uint8_t* ref, const uint8_t* cur, int width, int height,
                                   int blk, const int16_t* mvq, uint8_t* out5, int write_planes,

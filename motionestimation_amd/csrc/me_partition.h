@@ -1,7 +1,8 @@
 // me_partition.h -- the partition search's internal interface (include/me.h
 // "partition search"): what the host-only planner (me_partition_plan.cpp), the
 // kernels (me_partition.hip; their launchers are declared in me_kernels.h) and
-// the entry points share.  No HIP dependency.  Not installed.
+// the entry points share.  No HIP dependency (the kernels' shared device code is
+// me_partition_lane.h).  Not installed.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -36,6 +37,14 @@ ME_PART_HD inline int partition_fast_pitch(int range) { return 4 * (PART_TB * 4 
 ME_PART_HD inline int partition_fast_rows(int range) {
   const int chunks = (2 * range + 1 + PART_K - 1) / PART_K;
   return chunks * PART_K + 15;
+}
+
+// The rate-constrained fast kernel (me_partition_rd.hip) shares the geometry;
+// its dy rows per lane-task (DESIGN.md "Rate-constrained partition search").
+constexpr int PART_RD_K = 6;
+ME_PART_HD inline int partition_rd_fast_rows(int range) {
+  const int chunks = (2 * range + 1 + PART_RD_K - 1) / PART_RD_K;
+  return chunks * PART_RD_K + 15;
 }
 
 }  // namespace me

@@ -52,6 +52,16 @@ int me_partition_kernel_variant(int width, int height, int stride, int blk, int 
   return fast ? ME_PART_KERNEL_FAST : ME_PART_KERNEL_GENERIC;
 }
 
+int me_partition_rd_kernel_variant(int width, int height, int stride, int blk, int range,
+                                   uint32_t lambda) {
+  if (lambda > ME_PART_RD_MAX_LAMBDA) return -1;
+  const int v = me_partition_kernel_variant(width, height, stride, blk, range);
+  // The fast kernel holds a candidate's J in 26 bits of a 32-bit key, like
+  // me_rd_fast_kernel.
+  if (v == ME_PART_KERNEL_FAST && lambda > ME_RD_FAST_MAX_LAMBDA) return ME_PART_KERNEL_GENERIC;
+  return v;
+}
+
 me_status me_partition_leaf_field(int width, int height, int blk, const me_part_fields* in,
                                   int16_t* leaf) {
   int n[4];

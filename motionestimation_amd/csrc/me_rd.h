@@ -57,4 +57,11 @@ ME_RD_HD inline int rd_bits(int v) {
   return 63 - 2 * __builtin_clz(u);
 }
 
+#ifdef __HIPCC__
+// Saturating u32 add (v_add_u32 with clamp); me_rd.hip and me_partition_rd.hip.
+__device__ inline __attribute__((always_inline)) uint32_t add_sat(uint32_t a, uint32_t b) {
+  return __builtin_elementwise_add_sat(a, b);
+}
+#endif
+
 }  // namespace me

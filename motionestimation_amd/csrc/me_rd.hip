@@ -198,11 +198,6 @@ __device__ __forceinline__ void rd_lane(uint32_t at, int pitch, const uint32_t (
   });
 }
 
-// Saturating u32 add (v_add_u32 with clamp).
-__device__ __forceinline__ uint32_t add_sat(uint32_t a, uint32_t b) {
-  return __builtin_elementwise_add_sat(a, b);
-}
-
 // The lane's best 32-bit key J << 6 | 4 j + i, ordered like (J, dy, dx) within
 // the lane.  rx[i] = lambda bits(4 dx_i - px) << 6 | i and ry[j] = lambda
 // bits(4 dy_j - py) << 6 | 4 j come from the workgroup's rate tables: the sum

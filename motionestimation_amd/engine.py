@@ -123,6 +123,73 @@ class PartitionFields:
                                u(self.mode_cost) if self.mode_cost is not None else None)
 
 
+class PartRdFields(ctypes.Structure):
+    """include/me.h me_part_rd_fields."""
+    _fields_ = [("f", PartFields)] + [(n, ctypes.c_void_p) for n in
+                                      ("dist_2nx2n", "dist_2nxn", "dist_nx2n", "dist_nxn",
+                                       "bits_2nx2n", "bits_2nxn", "bits_nx2n", "bits_nxn")]
+
+
+class PartitionRdFields(PartitionFields):
+    """The records of a rate-constrained partition search: PartitionFields
+    (cost = J per cell) plus dist (four uint32 [cells], the SADs, or None) and
+    bits (four uint8 [cells], the rates, or None).  struct() is the
+    me_part_fields inside, so the leaf-field calls take these fields as they
+    are; rd_struct() is the whole me_part_rd_fields."""
+
+    def __init__(self, mv, cost, mode, mode_cost, dist, bits):
+        super().__init__(mv, cost, mode, mode_cost)
+        self.dist, self.bits = dist, bits
+
+    def rd_struct(self) -> PartRdFields:
+        ptr = (lambda a: a.ctypes.data) if isinstance(self.mode, np.ndarray) else \
+            (lambda a: a.data_ptr())
+        opt = lambda a: ptr(a) if a is not None else None
+        dist = self.dist if self.dist is not None else [None] * 4
+        bits = self.bits if self.bits is not None else [None] * 4
+        return PartRdFields(self.struct(), *[opt(a) for a in dist], *[opt(a) for a in bits])
+
+    @classmethod
+    def host(cls, width: int, height: int, blk: int) -> "PartitionRdFields":
+        n = partition_counts(width, height, blk)
+        return cls([np.zeros((k, 2), np.int16) for k in n], [np.zeros(k, np.uint32) for k in n],
+                   np.zeros(n[0], np.uint8), np.zeros(n[0], np.uint32),
+                   [np.zeros(k, np.uint32) for k in n], [np.zeros(k, np.uint8) for k in n])
+
+    @classmethod
+    def device(cls, width: int, height: int, blk: int, frames: int = 1, device="cuda"):
+        import torch
+        n = partition_counts(width, height, blk)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        return cls([z((frames * k, 2), torch.int16) for k in n],
+                   [z((frames * k,), torch.int32) for k in n],
+                   z((frames * n[0],), torch.uint8), z((frames * n[0],), torch.int32),
+                   [z((frames * k,), torch.int32) for k in n],
+                   [z((frames * k,), torch.uint8) for k in n])
+
+    def numpy(self) -> "PartitionRdFields":
+        """Host copy of device fields (costs and distortions as uint32)."""
+        u = lambda t: t.cpu().numpy().view(np.uint32)
+        return PartitionRdFields([t.cpu().numpy() for t in self.mv],
+                                 [u(t) for t in self.cost] if self.cost is not None else None,
+                                 self.mode.cpu().numpy(),
+                                 u(self.mode_cost) if self.mode_cost is not None else None,
+                                 [u(t) for t in self.dist] if self.dist is not None else None,
+                                 [t.cpu().numpy() for t in self.bits]
+                                 if self.bits is not None else None)
+
+
+def partition_rd_kernel_variant(width: int, height: int, stride: int, blk: int, span: int,
+                                lam: int) -> int:
+    """The kernel that takes the frame's full-size macroblocks in a
+    rate-constrained partition search (me_partition_rd_kernel_variant):
+    ME_PART_KERNEL_FAST, ME_PART_KERNEL_GENERIC, or -1 for arguments the search
+    rejects."""
+    if not 0 <= lam < 1 << 32:
+        return -1
+    return int(_lib.lib().me_partition_rd_kernel_variant(width, height, stride, blk, span, lam))
+
+
 def partition_leaf_field(width: int, height: int, blk: int, fields: PartitionFields):
     """The leaf field (int16 [nhx * nhy, 2], block size blk / 2) of one frame's
     host fields, on the host (me_partition_leaf_field: no context, no GPU)."""
@@ -446,6 +513,26 @@ class Engine:
                                       _ptr(mv), _ptr(j), _ptr(d), _ptr(r)), self._h)
         return mv[:n], j[:n], d[:n], r[:n]
 
+    def partition_rd_search(self, ref, cur, blk: int, span: int, lam: int = 0, pred=None,
+                            cost="sad", width=None) -> "PartitionRdFields":
+        """partition_search on J = SAD + lam * bits(4 mv - pred) per partition,
+        the mode priced by its code length (me_partition_rd_search); pred int16
+        [macroblocks, 2] in quarter-pel units or None (all zero).  Returns
+        PartitionRdFields of numpy arrays."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        cur = np.ascontiguousarray(cur, dtype=np.uint8)
+        if ref.ndim != 2 or ref.shape != cur.shape:
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {ref.shape} vs {cur.shape}")
+        h, pitch = ref.shape
+        w = width or pitch
+        out = PartitionRdFields.host(w, h, blk)
+        pred = self._pred(pred, out.mode.size)
+        st = out.rd_struct()
+        check(_lib.lib().me_partition_rd_search(
+            self._h, _ptr(ref), _ptr(cur), w, h, pitch, blk, span, cost_code(cost), lam,
+            _ptr(pred) if pred is not None else None, ctypes.byref(st)), self._h)
+        return out
+
     def refine_qpel_rd(self, ref, cur, blk: int, mv, lam: int = 0, pred=None, cost="ssd",
                        stride=None):
         """refine_qpel on cost + lam * bits(q - pred) (me_refine_qpel_rd).
@@ -757,6 +844,33 @@ class Engine:
             s = fn(*args)
             if s:
                 check(s, ctx)
+        return run
+
+    def partition_rd_search_device(self, ref_t, cur_t, blk: int, span: int, lam: int, fields,
+                                   pred_t=None, cost="sad", stream=None, width=None, height=None):
+        """Enqueue the rate-constrained partition search of resident frames
+        (me_partition_rd_search_device): partition_search_device's arguments
+        with fields a PartitionRdFields of torch tensors
+        (PartitionRdFields.device) and pred_t the macroblocks' quarter-pel
+        predictors int16 [F * macroblocks, 2] or None (all zero)."""
+        self.prepared_partition_rd_search(ref_t, cur_t, blk, span, lam, fields, pred_t, cost,
+                                          stream, width, height)()
+
+    def prepared_partition_rd_search(self, ref_t, cur_t, blk, span, lam, fields, pred_t=None,
+                                     cost="sad", stream=None, width=None, height=None):
+        """Zero-argument callable enqueueing partition_rd_search_device(...) with these buffers."""
+        frames, rfs, cfs, w, h, pitch = self._plane_args(ref_t, cur_t, width, height)
+        st = fields.rd_struct()
+        fn, ctx = _lib.lib().me_partition_rd_search_device, self._h
+        args = (ctx, ref_t.data_ptr(), rfs, cur_t.data_ptr(), cfs, w, h, pitch, blk, span,
+                cost_code(cost), lam, frames, pred_t.data_ptr() if pred_t is not None else None,
+                ctypes.byref(st), stream if stream is not None else _current_stream())
+
+        def run():
+            s = fn(*args)
+            if s:
+                check(s, ctx)
+        run.fields = st  # keep the pointer struct alive with the callable
         return run
 
     def refine_qpel_rd_device(self, ref_t, cur_t, blk: int, cost, lam: int, mv_t, q_t=None,
