@@ -65,10 +65,36 @@ typedef enum {
 typedef enum {
   ME_COST_SSD = 0, /* reference parity: float MSE argmin; cost = SSD */
   ME_COST_SAD = 1, /* sum of absolute differences */
-  ME_COST_SSIM = 2 /* reference parity with src/common/ssim.c: float SSIM argmax
-                      (first strict maximum above 0); cost = the score's float
-                      bits; MV (0, 0) and cost 0 where no score is above 0 */
+  ME_COST_SSIM = 2, /* reference parity with src/common/ssim.c: float SSIM argmax
+                       (first strict maximum above 0); cost = the score's float
+                       bits; MV (0, 0) and cost 0 where no score is above 0 */
+  ME_COST_SATD = 3  /* sum of absolute 4x4 Hadamard-transformed differences
+                       ("SATD cost" below): the quarter-pel refinements and the
+                       bi-prediction only; every integer search returns
+                       ME_EUNSUPPORTED for it */
 } me_cost;
+
+/* ---- SATD cost (ME_COST_SATD) ----
+ * Exact integers; no reference counterpart, parity is against the numpy
+ * restatement tests/satd_ref.py.  For a block clipped to bw x bh with
+ * prediction P and current block C:
+ *   - residual: d(i, j) = C(i, j) - P(i, j) inside the block, 0 outside.
+ *   - tiles: a 4x4 grid anchored at the block's own top-left, ceil(bw / 4) x
+ *     ceil(bh / 4) tiles, partial tiles zero padded; every block_size in
+ *     [1, 64] (a 1x1 block is one tile with one non-zero residual).
+ *   - transform: T = H D H^T per tile, H the order-4 +-1 Hadamard matrix (sum
+ *     |T| does not depend on the row order of H).
+ *   - satd = (sum over tiles of sum |T_uv|) >> 1.  The shift is exact: the 16
+ *     coefficients of a tile all have the parity of the tile's residual sum.
+ *   - bounds: |T_uv| <= 16 * 255 = 4080; a tile's satd <= 8160; a 64x64
+ *     block's <= 2,088,960, so satd + 66 * 2^24 < 2^32 and ME_RD_MAX_LAMBDA
+ *     holds for the rate-constrained refinement as it is.
+ *   - identities: SAD <= 2 satd <= 16 SAD, and per tile sum T^2 = 16 sum d^2.
+ * Where it is accepted only cost(.) changes: stages, candidate order, carried
+ * centre, strict <, tie rules, edge replication and mode order are those of
+ * the entry point.  The composite entry points (me_full_search_qpel,
+ * me_full_search_rd_qpel, me_full_search_bipred) run their integer searches at
+ * ME_COST_SAD and everything after them at SATD. */
 
 /* Limits of this build. */
 #define ME_MAX_BLOCK 64    /* block_size in [1, 64]  (SSD of 64x64 < 2^32) */
@@ -370,7 +396,8 @@ me_status me_compensate_planes(me_ctx* ctx, const uint8_t* ref,
  *     order (dy outer), a candidate wins only with a strictly smaller cost, so
  *     ties go to the centre, then to the first candidate.  No window: the
  *     result is within 3 quarter units of 4 * m per axis.
- *   - ME_COST_SAD and ME_COST_SSD; ME_COST_SSIM returns ME_EUNSUPPORTED.
+ *   - ME_COST_SAD, ME_COST_SSD and ME_COST_SATD; ME_COST_SSIM returns
+ *     ME_EUNSUPPORTED.
  * Whole frames on one device only: a stripe would need reference rows beyond
  * its documented cover (3 more above and below), and a multi-device context's
  * stripes likewise, so neither is offered. */
@@ -401,8 +428,9 @@ me_status me_refine_qpel(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, in
                          const int16_t* mv_xy, int16_t* mv_q, uint32_t* block_cost);
 
 /* me_full_search and the refinement back to back on the device: the integer
- * field never visits the host.  One context device (ME_EUNSUPPORTED with
- * several). */
+ * field never visits the host.  With ME_COST_SATD the integer search runs at
+ * ME_COST_SAD and the refinement at SATD.  One context device
+ * (ME_EUNSUPPORTED with several). */
 me_status me_full_search_qpel(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int width,
                               int height, int stride, int block_size, int search_range,
                               me_cost cost, int16_t* mv_q, uint32_t* block_cost);
@@ -425,8 +453,8 @@ me_status me_compensate_planes_qpel(me_ctx* ctx, const uint8_t* ref, const uint8
  * quarter-pel prediction blocks defined above, from ref0 / ref1:
  *   - bi-prediction sample: PB(q0, q1) = (P0(q0) + P1(q1) + 1) >> 1 per pixel
  *     (H.264 default weighting).
- *   - costs of a block (partial edge blocks keep their true size), SAD or SSD
- *     against the current block: c0 = cost(P0(q0)), c1 = cost(P1(q1)),
+ *   - costs of a block (partial edge blocks keep their true size), SAD, SSD
+ *     or SATD against the current block: c0 = cost(P0(q0)), c1 = cost(P1(q1)),
  *     cb = cost(PB(b0, b1)), (b0, b1) starting at (q0, q1).
  *   - joint refinement (refine != 0): two passes at quarter step, each over
  *     the eight neighbours + (dx, dy), dx, dy in {-1, 0, 1}, in raster order
@@ -473,8 +501,9 @@ me_status me_bipred(me_ctx* ctx, const uint8_t* ref0, const uint8_t* ref1, const
 
 /* Both integer searches (ref0 and ref1 against cur), both quarter-pel
  * refinements, then the bi-prediction with refine = 1, back to back on the
- * device: no field visits the host.  One context device (ME_EUNSUPPORTED with
- * several).  block_cost may be NULL. */
+ * device: no field visits the host.  With ME_COST_SATD both integer searches
+ * run at ME_COST_SAD, both refinements and the bi-prediction at SATD.  One
+ * context device (ME_EUNSUPPORTED with several).  block_cost may be NULL. */
 me_status me_full_search_bipred(me_ctx* ctx, const uint8_t* ref0, const uint8_t* ref1,
                                 const uint8_t* cur, int width, int height, int stride,
                                 int block_size, int search_range, me_cost cost, int16_t* mv_out0,
@@ -632,7 +661,7 @@ me_status me_partition_leaf_field(int width, int height, int block_size,
  *     costs are me_full_search's at SAD bit for bit, whatever the predictor.
  *   - refinement: me_refine_qpel's procedure (stages, candidate order, centre
  *     carried, strict <) on Jq(q) = cost(P(q)) + lambda * (bits(qx - px) +
- *     bits(qy - py)), cost SAD or SSD.  Outputs mv_q, block_cost = Jq,
+ *     bits(qy - py)), cost SAD, SSD or SATD.  Outputs mv_q, block_cost = Jq,
  *     block_dist = cost(P(mv_q)).  With lambda = 0 it is me_refine_qpel bit for
  *     bit.  Jq < 2^32 for SSD too (64 * 64 * 255^2 + 66 * 2^24).
  *   - limits: the search costs ME_COST_SAD only (SSD and SSIM:
@@ -700,8 +729,9 @@ me_status me_refine_qpel_rd(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur,
 
 /* me_rd_search then me_refine_qpel_rd back to back on the device with the same
  * predictor and lambda, as me_full_search_qpel does: the integer field never
- * visits the host.  ME_COST_SAD (the search's limit).  One context device.
- * pred_q and block_cost may be NULL. */
+ * visits the host.  ME_COST_SAD (the search's limit), or ME_COST_SATD: the
+ * search then runs at SAD and the refinement at SATD, the encoder's usual
+ * split.  One context device.  pred_q and block_cost may be NULL. */
 me_status me_full_search_rd_qpel(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int width,
                                  int height, int stride, int block_size, int search_range,
                                  me_cost cost, uint32_t lambda, const int16_t* pred_q,

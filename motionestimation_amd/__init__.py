@@ -5,7 +5,8 @@ The compute path is libme_hip.so (HIP kernels for gfx950 behind the C ABI of
 include/me.h); this package is the host-side mirror of the reference's
 interface over that ABI.  There is no CPU fallback.
 """
-from ._lib import (ME_COST_SAD, ME_COST_SSD, ME_COST_SSIM, ME_ECOMM, ME_EDEVICE,  # noqa: F401
+from ._lib import (ME_COST_SAD, ME_COST_SATD, ME_COST_SSD, ME_COST_SSIM, ME_ECOMM,  # noqa: F401
+                   ME_EDEVICE,
                    ME_BIPRED_MAX_Q, ME_PART_2Nx2N, ME_PART_2NxN, ME_PART_KERNEL_FAST,
                    ME_PART_KERNEL_GENERIC, ME_PART_MAX_LAMBDA, ME_PART_MAX_RANGE, ME_PART_Nx2N,
                    ME_PART_NxN, ME_PART_RD_MAX_LAMBDA, ME_PRED_BI, ME_PRED_L0, ME_PRED_L1,

@@ -19,7 +19,7 @@ ME_OK, ME_EINVAL, ME_ENOMEM, ME_EDEVICE, ME_ECOMM, ME_EUNSUPPORTED, ME_EIO = ran
 ME_COMM_ID_BYTES = 128  # include/me.h (sizeof ncclUniqueId)
 ME_COMM_TIMEOUT_MS = 60000
 ME_YUV_LUMA, ME_YUV_I420 = 0, 1
-ME_COST_SSD, ME_COST_SAD, ME_COST_SSIM = 0, 1, 2
+ME_COST_SSD, ME_COST_SAD, ME_COST_SSIM, ME_COST_SATD = 0, 1, 2, 3
 ME_PATH_AUTO, ME_PATH_VALU, ME_PATH_MFMA_TILES, ME_PATH_MFMA_LEAN, ME_PATH_MFMA_PREPASS = 0, 1, 2, 3, 4
 ME_PATH_PROCESS = -1
 ME_SEARCH_PATH_SSIM, ME_SEARCH_PATH_SSIM_MFMA = 7, 8  # float-chain / matrix-core SSIM kernels

@@ -180,6 +180,14 @@ me_status grow(me_ctx* c, void** p, size_t* cap, size_t need) {
   return ME_OK;
 }
 
+// SATD costs sub-pel candidates only: the quarter-pel refinements and the
+// bi-prediction take it, their composite entry points search at SAD first
+// (search_cost), and an integer search asked for it is a valid request this
+// build does not serve.
+static const char SATD_NO_SEARCH[] =
+    "integer searches have no SATD cost (quarter-pel refinement and bi-prediction only)";
+static me_cost search_cost(me_cost cost) { return cost == ME_COST_SATD ? ME_COST_SAD : cost; }
+
 me_status check_args(me_ctx* c, const void* ref, const void* cur, int width, int height,
                      int stride, int blk, int range, int cost, const void* mv) {
   if (!c) return ME_EINVAL;
@@ -188,8 +196,10 @@ me_status check_args(me_ctx* c, const void* ref, const void* cur, int width, int
   if (stride < width) return fail(c, ME_EINVAL, "stride %d < width %d", stride, width);
   if (blk < 1 || blk > ME_MAX_BLOCK) return fail(c, ME_EINVAL, "block_size %d", blk);
   if (range < 0 || range > ME_MAX_RANGE) return fail(c, ME_EINVAL, "search_range %d", range);
-  if (cost != ME_COST_SSD && cost != ME_COST_SAD && cost != ME_COST_SSIM)
+  if (cost != ME_COST_SSD && cost != ME_COST_SAD && cost != ME_COST_SSIM && cost != ME_COST_SATD)
     return fail(c, ME_EINVAL, "cost %d", cost);
+  // (the sub-pel entry points pass search_cost(cost): SATD never arrives from them)
+  if (cost == ME_COST_SATD) return fail(c, ME_EUNSUPPORTED, "%s", SATD_NO_SEARCH);
   // Buffer descriptors carry 32-bit byte ranges: planes stay below 2 GiB.
   if ((long long)stride * height >= (1LL << 31))
     return fail(c, ME_EUNSUPPORTED, "plane of %lld bytes (limit 2 GiB)",
@@ -446,6 +456,7 @@ namespace {
 using me::fail;
 using me::grow;
 using me::check_args;
+using me::search_cost;
 using me::make_args;
 using me::attach_scratch;
 using me::launch_ordered;
@@ -1121,7 +1132,7 @@ me_status me_compensate_planes(me_ctx* c, const uint8_t* ref, const uint8_t* cur
 static me_status check_qpel(me_ctx* c, me_cost cost, const void* mv_q) {
   if (!mv_q) return me::fail(c, ME_EINVAL, "null quarter-pel output");
   if (cost == ME_COST_SSIM)
-    return me::fail(c, ME_EUNSUPPORTED, "quarter-pel refinement has no SSIM cost (SAD or SSD)");
+    return me::fail(c, ME_EUNSUPPORTED, "quarter-pel refinement has no SSIM cost (SAD, SSD or SATD)");
   return ME_OK;
 }
 
@@ -1136,7 +1147,7 @@ static me_status refine_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rfs,
     if (st != ME_OK) return st;
   }
   const hipError_t e = me::launch_qpel_refine(d_ref, rfs, d_cur, cfs, width, height, stride, blk,
-                                              cost == ME_COST_SSD, n_frames, d_mv, d_q, d_cost, s);
+                                              cost, n_frames, d_mv, d_q, d_cost, s);
   if (e != hipSuccess)
     return me::fail(c, ME_EDEVICE, "quarter-pel refinement launch: %s", hipGetErrorString(e));
   return ME_OK;
@@ -1149,7 +1160,8 @@ me_status me_refine_qpel_device(me_ctx* c, const uint8_t* d_ref, size_t ref_fram
                                 void* stream) {
   if (!c) return ME_EINVAL;
   if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
-  me_status s = check_args(c, d_ref, d_cur, width, height, stride, blk, 0, cost, d_mv_xy);
+  me_status s =
+      check_args(c, d_ref, d_cur, width, height, stride, blk, 0, search_cost(cost), d_mv_xy);
   if (s != ME_OK) return s;
   if ((s = check_qpel(c, cost, d_mv_q)) != ME_OK) return s;
   // frames must not overlap and a plane stack stays below 2 GiB, as in
@@ -1187,7 +1199,7 @@ static me_status upload_pair(me_ctx* c, Dev& d, const uint8_t* ref, const uint8_
 me_status me_refine_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width, int height,
                          int stride, int blk, me_cost cost, const int16_t* mv_xy, int16_t* mv_q,
                          uint32_t* block_cost) {
-  me_status s = check_args(c, ref, cur, width, height, stride, blk, 0, cost, mv_xy);
+  me_status s = check_args(c, ref, cur, width, height, stride, blk, 0, search_cost(cost), mv_xy);
   if (s != ME_OK) return s;
   if ((s = check_qpel(c, cost, mv_q)) != ME_OK) return s;
   const size_t nb = (size_t)me_num_blocks(width, height, blk);
@@ -1214,7 +1226,8 @@ me_status me_refine_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int 
 me_status me_full_search_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
                               int height, int stride, int blk, int range, me_cost cost,
                               int16_t* mv_q, uint32_t* block_cost) {
-  me_status s = check_args(c, ref, cur, width, height, stride, blk, range, cost, mv_q);
+  me_status s =
+      check_args(c, ref, cur, width, height, stride, blk, range, search_cost(cost), mv_q);
   if (s != ME_OK) return s;
   if ((s = check_qpel(c, cost, mv_q)) != ME_OK) return s;
   if (c->devs.size() > 1)
@@ -1228,7 +1241,8 @@ me_status me_full_search_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur,
   uint32_t* dcost = reinterpret_cast<uint32_t*>(d.rec + nb * 4);
   const int nby = (height + blk - 1) / blk;
   const me::SearchJob J{d.ref, 0, d.cur, 0, 0, nby, dmv, dcost};
-  me::SearchArgs p = make_args(J, width, height, width, blk, range, cost);
+  // (SATD: the integer search runs at SAD)
+  me::SearchArgs p = make_args(J, width, height, width, blk, range, search_cost(cost));
   if ((s = attach_scratch(c, d, p)) != ME_OK) return s;
   if ((s = launch_ordered(c, d, p, &J, 1, d.stream)) != ME_OK) return s;
   // the searched vectors stay inside the window (|m| <= ME_MAX_RANGE): refine in place
@@ -1260,7 +1274,7 @@ static me_status check_bipred(me_ctx* c, me_cost cost, const void* ref1, const v
   if (!ref1 || !q1 || !out0 || !out1 || !mode)
     return me::fail(c, ME_EINVAL, "null bi-prediction plane, field or mode pointer");
   if (cost == ME_COST_SSIM)
-    return me::fail(c, ME_EUNSUPPORTED, "bi-prediction has no SSIM cost (SAD or SSD)");
+    return me::fail(c, ME_EUNSUPPORTED, "bi-prediction has no SSIM cost (SAD, SSD or SATD)");
   return ME_OK;
 }
 
@@ -1277,7 +1291,7 @@ static me_status bipred_on(me_ctx* c, Dev& d, const uint8_t* d_ref0, size_t r0fs
     if (st != ME_OK) return st;
   }
   const hipError_t e = me::launch_bipred(d_ref0, r0fs, d_ref1, r1fs, d_cur, cfs, width, height,
-                                         stride, blk, cost == ME_COST_SSD, refine, n_frames, q0, q1,
+                                         stride, blk, cost, refine, n_frames, q0, q1,
                                          out0, out1, mode, d_cost, d_cost3, s);
   if (e != hipSuccess)
     return me::fail(c, ME_EDEVICE, "bi-prediction launch: %s", hipGetErrorString(e));
@@ -1293,7 +1307,8 @@ me_status me_bipred_device(me_ctx* c, const uint8_t* d_ref0, size_t ref0_frame_s
                            void* stream) {
   if (!c) return ME_EINVAL;
   if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
-  me_status s = check_args(c, d_ref0, d_cur, width, height, stride, blk, 0, cost, d_mv_q0);
+  me_status s =
+      check_args(c, d_ref0, d_cur, width, height, stride, blk, 0, search_cost(cost), d_mv_q0);
   if (s != ME_OK) return s;
   if ((s = check_bipred(c, cost, d_ref1, d_mv_q1, d_mv_out0, d_mv_out1, d_mode)) != ME_OK) return s;
   // frames must not overlap and a plane stack stays below 2 GiB, as in
@@ -1350,7 +1365,8 @@ me_status me_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* ref1, const u
                     int width, int height, int stride, int blk, me_cost cost, int refine,
                     const int16_t* mv_q0, const int16_t* mv_q1, int16_t* mv_out0,
                     int16_t* mv_out1, uint8_t* mode, uint32_t* block_cost, uint32_t* cost3) {
-  me_status s = check_args(c, ref0, cur, width, height, stride, blk, 0, cost, mv_q0);
+  me_status s =
+      check_args(c, ref0, cur, width, height, stride, blk, 0, search_cost(cost), mv_q0);
   if (s != ME_OK) return s;
   if ((s = check_bipred(c, cost, ref1, mv_q1, mv_out0, mv_out1, mode)) != ME_OK) return s;
   const size_t nb = (size_t)me_num_blocks(width, height, blk);
@@ -1382,7 +1398,8 @@ me_status me_full_search_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* r
                                 const uint8_t* cur, int width, int height, int stride, int blk,
                                 int range, me_cost cost, int16_t* mv_out0, int16_t* mv_out1,
                                 uint8_t* mode, uint32_t* block_cost) {
-  me_status s = check_args(c, ref0, cur, width, height, stride, blk, range, cost, mv_out0);
+  me_status s =
+      check_args(c, ref0, cur, width, height, stride, blk, range, search_cost(cost), mv_out0);
   if (s != ME_OK) return s;
   if ((s = check_bipred(c, cost, ref1, mv_out1, mv_out0, mv_out1, mode)) != ME_OK) return s;
   if (c->devs.size() > 1)
@@ -1400,7 +1417,8 @@ me_status me_full_search_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* r
   int16_t* fields[2] = {B.q0, B.q1};
   for (int k = 0; k < 2; k++) {
     const me::SearchJob J{refs[k], 0, d.cur, 0, 0, nby, fields[k], B.cost};
-    me::SearchArgs p = make_args(J, width, height, width, blk, range, cost);
+    // (SATD: the integer searches run at SAD)
+    me::SearchArgs p = make_args(J, width, height, width, blk, range, search_cost(cost));
     if ((s = attach_scratch(c, d, p)) != ME_OK) return s;
     if ((s = launch_ordered(c, d, p, &J, 1, d.stream)) != ME_OK) return s;
     // the searched vectors stay inside the window (|m| <= ME_MAX_RANGE): refine in place
@@ -1483,7 +1501,7 @@ static me_status check_partition(me_ctx* c, const void* ref, const void* cur, in
   if (!ref || !cur || !out) return fail(c, ME_EINVAL, "null plane or field pointer");
   if (!out->mv_2nx2n || !out->mv_2nxn || !out->mv_nx2n || !out->mv_nxn || !out->mode)
     return fail(c, ME_EINVAL, "null partition vector field or mode array");
-  if (cost != ME_COST_SSD && cost != ME_COST_SAD && cost != ME_COST_SSIM)
+  if (cost != ME_COST_SSD && cost != ME_COST_SAD && cost != ME_COST_SSIM && cost != ME_COST_SATD)
     return fail(c, ME_EINVAL, "cost %d", (int)cost);
   const char* why = "";
   const me_status s = me::partition_check(width, height, stride, blk, range, &why);
@@ -1634,7 +1652,7 @@ static me_status check_rd(me_ctx* c, const void* ref, const void* cur, int width
   if (!c) return ME_EINVAL;
   if (!ref || !cur || !mv || !block_cost)
     return fail(c, ME_EINVAL, "null plane, vector or cost pointer");
-  if (cost != ME_COST_SSD && cost != ME_COST_SAD && cost != ME_COST_SSIM)
+  if (cost != ME_COST_SSD && cost != ME_COST_SAD && cost != ME_COST_SSIM && cost != ME_COST_SATD)
     return fail(c, ME_EINVAL, "cost %d", (int)cost);
   const char* why = "";
   const me_status s = me::rd_check(width, height, stride, blk, range, lambda, &why);
@@ -1694,7 +1712,7 @@ static me_status refine_rd_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rf
     if (st != ME_OK) return st;
   }
   const hipError_t e = me::launch_qpel_refine_rd(d_ref, rfs, d_cur, cfs, width, height, stride,
-                                                 blk, cost == ME_COST_SSD, lambda, n_frames,
+                                                 blk, cost, lambda, n_frames,
                                                  d_pred, d_mv, d_q, d_cost, d_dist, s);
   if (e != hipSuccess)
     return me::fail(c, ME_EDEVICE, "rate-constrained refinement launch: %s",
@@ -1774,7 +1792,8 @@ me_status me_refine_qpel_rd_device(me_ctx* c, const uint8_t* d_ref, size_t ref_f
                                    int16_t* d_mv_q, uint32_t* d_block_cost,
                                    uint32_t* d_block_dist, void* stream) {
   if (!c) return ME_EINVAL;
-  me_status s = check_args(c, d_ref, d_cur, width, height, stride, blk, 0, cost, d_mv_xy);
+  me_status s =
+      check_args(c, d_ref, d_cur, width, height, stride, blk, 0, search_cost(cost), d_mv_xy);
   if (s != ME_OK) return s;
   if ((s = check_qpel(c, cost, d_mv_q)) != ME_OK) return s;
   if ((s = check_rd_ctx(c, lambda, "rate-constrained refinement")) != ME_OK) return s;
@@ -1791,7 +1810,7 @@ me_status me_refine_qpel_rd(me_ctx* c, const uint8_t* ref, const uint8_t* cur, i
                             int height, int stride, int blk, me_cost cost, uint32_t lambda,
                             const int16_t* pred_q, const int16_t* mv_xy, int16_t* mv_q,
                             uint32_t* block_cost, uint32_t* block_dist) {
-  me_status s = check_args(c, ref, cur, width, height, stride, blk, 0, cost, mv_xy);
+  me_status s = check_args(c, ref, cur, width, height, stride, blk, 0, search_cost(cost), mv_xy);
   if (s != ME_OK) return s;
   if ((s = check_qpel(c, cost, mv_q)) != ME_OK) return s;
   if ((s = check_rd_ctx(c, lambda, "rate-constrained refinement")) != ME_OK) return s;
@@ -1824,7 +1843,9 @@ me_status me_full_search_rd_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* c
                                  uint32_t lambda, const int16_t* pred_q, int16_t* mv_q,
                                  uint32_t* block_cost) {
   // (block_cost is optional here: the search's own cost array is d.rec's)
-  me_status s = check_rd(c, ref, cur, width, height, stride, blk, range, cost, lambda, mv_q, mv_q);
+  // (SATD: the search runs at SAD, the refinement at SATD)
+  me_status s = check_rd(c, ref, cur, width, height, stride, blk, range, search_cost(cost), lambda,
+                         mv_q, mv_q);
   if (s != ME_OK) return s;
   c->err[0] = 0;
   Dev& d = c->devs[0];

@@ -49,7 +49,8 @@ bool valid_header(const me_mv_header& h) {
   if (!(memcmp(h.magic, "MEMV", 4) == 0 && h.version == 1 && h.flags <= 3 && h.width > 0 &&
         h.height > 0 && h.block_size > 0 && h.block_size <= ME_MAX_BLOCK &&
         h.search_range >= 0 &&
-        (h.cost == ME_COST_SSD || h.cost == ME_COST_SAD || h.cost == ME_COST_SSIM)))
+        (h.cost == ME_COST_SSD || h.cost == ME_COST_SAD || h.cost == ME_COST_SSIM ||
+         h.cost == ME_COST_SATD)))
     return false;
   // the block count fits an int and the whole file an int64 (hostile headers)
   if (me_num_blocks(h.width, h.height, h.block_size) <= 0) return false;

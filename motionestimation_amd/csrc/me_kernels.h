@@ -129,14 +129,14 @@ hipError_t launch_partition_leaf(int width, int height, int blk, int n_frames,
 // be null; any int16 vector reads inside the planes.  No context scratch.
 hipError_t launch_qpel_refine(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
                               size_t cur_frame_stride, int width, int height, int stride, int blk,
-                              bool ssd, int n_frames, const int16_t* mv_in, int16_t* mv_out,
+                              int cost, int n_frames, const int16_t* mv_in, int16_t* mv_out,
                               uint32_t* cost_out, hipStream_t stream);
 // launch_qpel_refine on cost + lambda * bits(q - pred) (include/me.h
 // "rate-constrained motion search"): pred laid out like mv_in, null = all zero;
 // cost_out (J) and dist_out (the cost at the result) may be null.
 hipError_t launch_qpel_refine_rd(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
                                  size_t cur_frame_stride, int width, int height, int stride,
-                                 int blk, bool ssd, uint32_t lambda, int n_frames,
+                                 int blk, int cost, uint32_t lambda, int n_frames,
                                  const int16_t* pred, const int16_t* mv_in, int16_t* mv_out,
                                  uint32_t* cost_out, uint32_t* dist_out, hipStream_t stream);
 // Rate-constrained integer search (me_rd.hip; geometry in me_rd.h).  n_frames
@@ -171,7 +171,7 @@ hipError_t launch_qpel_compensate(const uint8_t* ref, const uint8_t* cur, int wi
 // scratch; any int16 vector reads inside the planes.
 hipError_t launch_bipred(const uint8_t* ref0, size_t ref0_frame_stride, const uint8_t* ref1,
                          size_t ref1_frame_stride, const uint8_t* cur, size_t cur_frame_stride,
-                         int width, int height, int stride, int blk, bool ssd, int refine,
+                         int width, int height, int stride, int blk, int cost, int refine,
                          int n_frames, const int16_t* q0_in, const int16_t* q1_in, int16_t* q0_out,
                          int16_t* q1_out, uint8_t* mode_out, uint32_t* cost_out,
                          uint32_t* cost3_out, hipStream_t stream);

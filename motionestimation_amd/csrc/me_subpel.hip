@@ -23,7 +23,8 @@
 //            adjacent bytes: a lane takes 4 pixels of a candidate as two
 //            aligned dwords and one v_alignbyte, and costs them with one
 //            v_sad_u8 (SAD) or two v_dot4_u32_u8 (SSD = sum p^2 - 2 sum pc +
-//            sum c^2).
+//            sum c^2); for SATD the 4 pixels are one row of a 4x4 Hadamard tile
+//            (satd4 below).
 // A candidate (or the compensated block) is, per pixel, the rounded average of
 // two hg samples at offsets that are uniform over the block.
 #include <hip/hip_runtime.h>
@@ -209,13 +210,76 @@ struct QpelPix {
   uint32_t cur[QpelGeom<TB>::GPL], mask[QpelGeom<TB>::GPL];
 };
 
+// ---- SATD (include/me.h "SATD cost"; DESIGN.md "SATD cost") ----
+//
+// A lane's group of 4 adjacent pixels is one row of a 4x4 tile anchored at the
+// block's top-left, and the tile's other rows are the groups of the lanes
+// lane ^ GW and lane ^ 2 GW (group g is row g / GW; with GPL > 1 group k of a
+// lane is NT / GW rows, a multiple of 4, further down: tiles of its own).  The
+// transform is four butterfly stages that commute: two over the row's pixels
+// inside the lane, two over the tile's rows across lanes, on packed int16
+// (|T| <= 16 * 255).  The fourth stage is never formed: |a + b| + |a - b| =
+// 2 max(|a|, |b|), so sum max(|a|, |b|) over the pairs is sum |T| / 2, the
+// satd itself with its shift.  Bytes outside a partial block are 0 on both
+// sides (QpelPix::mask): the zero padding of the definition.  Every lane of
+// the wave calls this, the lanes without pixels included (they hold zeros).
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ s16x2 as_s16x2(uint32_t v) { return __builtin_bit_cast(s16x2, v); }
+
+// Lane ^ M's v.  Inside a row of 16 lanes a DPP move: a quad permutation for
+// M = 1, 2; row_ror:8 is the exchange itself for M = 8; for M = 4 row_ror:4
+// serves the lanes whose bit 2 is set (banks 1 and 3) and row_ror:12 the
+// others.  Across rows the LDS crossbar.  Every lane of the wave is active.
+template <int M>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t v) {
+  const int x = (int)v;
+  if (M == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false);
+  if (M == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false);
+  if (M == 4) {
+    const int t = __builtin_amdgcn_update_dpp(0, x, 0x124, 0xF, 0xA, false);  // row_ror:4
+    return (uint32_t)__builtin_amdgcn_update_dpp(t, x, 0x12C, 0xF, 0x5, false);  // row_ror:12
+  }
+  if (M == 8) return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, false);
+  return (uint32_t)__shfl_xor(x, M, 64);
+}
+
+// v + partner in the lane whose bit M is clear, partner - v in lane ^ M.
+template <int M>
+__device__ __forceinline__ s16x2 satd_rows(s16x2 v) {
+  const s16x2 partner = as_s16x2(lane_xor<M>(__builtin_bit_cast(uint32_t, v)));
+  const short sg = (threadIdx.x & M) ? -1 : 1;
+  return v * s16x2{sg, sg} + partner;
+}
+
+// The lane's share of the satd of prediction bytes p against cur bytes c.
+template <int TB>
+__device__ __forceinline__ uint32_t satd4(uint32_t p, uint32_t c) {
+  constexpr int GW = QpelGeom<TB>::GW;
+  // residuals of pixels (0, 2) and (1, 3)
+  s16x2 e = as_s16x2(p & 0x00FF00FFu) - as_s16x2(c & 0x00FF00FFu);
+  s16x2 o = as_s16x2((p >> 8) & 0x00FF00FFu) - as_s16x2((c >> 8) & 0x00FF00FFu);
+  // (x, y) -> (x + y, x - y): pixels 0 with 2, 1 with 3
+  e = e * s16x2{1, -1} + e.yx;
+  o = o * s16x2{1, -1} + o.yx;
+  e = satd_rows<GW>(e);
+  o = satd_rows<GW>(o);
+  e = satd_rows<2 * GW>(e);
+  o = satd_rows<2 * GW>(o);
+  // pixels (0, 2) with (1, 3): the stage that is not formed
+  const s16x2 m = __builtin_elementwise_max(__builtin_elementwise_abs(e),
+                                            __builtin_elementwise_abs(o));
+  return (uint32_t)m.x + (uint32_t)m.y;
+}
+
 // Costs of the candidates centre + step * (dx, dy), dx, dy in {-1, 0, 1}, in
 // raster order into out[0..9) (out[4], the centre, only when CENTRE), summed
 // over the block: every thread returns the same nine numbers.
-template <int TB, bool SSD, bool CENTRE>
+template <int TB, int COST, bool CENTRE>
 __device__ __forceinline__ void qpel_costs(QpelLds<TB>& s, const QpelPix<TB>& P, uint32_t cc,
                                            int cx, int cy, int step, uint32_t (&out)[9]) {
   using G = QpelGeom<TB>;
+  constexpr bool SSD = COST == ME_COST_SSD;
   uint32_t acc[9];
 #pragma unroll
   for (int n = 0; n < 9; n++) {
@@ -227,7 +291,9 @@ __device__ __forceinline__ void qpel_costs(QpelLds<TB>& s, const QpelPix<TB>& P,
     for (int k = 0; k < G::GPL; k++) {
       // bytes outside a partial block are 0 on both sides and cost nothing
       const uint32_t p = qpel_pred4<TB>(s, P.px0[k], P.py[k], t) & P.mask[k];
-      if (SSD) {
+      if (COST == ME_COST_SATD) {
+        pp += satd4<TB>(p, P.cur[k]);
+      } else if (SSD) {
         pp = __builtin_amdgcn_udot4(p, p, pp, false);
         pc = __builtin_amdgcn_udot4(p, P.cur[k], pc, false);
       } else {
@@ -284,12 +350,13 @@ __device__ __forceinline__ void qpel_pixels(QpelPix<TB>& P, const uint8_t* __res
 // One block (workgroup) per macroblock, the frame in blockIdx.y.  mv_in and
 // mv_out may be the same array: a block reads its own record before its first
 // barrier and writes it after its last.
-template <int TB, bool SSD>
+template <int TB, int COST>
 __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_qpel_refine_kernel(
     const uint8_t* __restrict__ ref, size_t ref_frame_stride, const uint8_t* __restrict__ cur,
     size_t cur_frame_stride, int width, int height, int stride, int blk, int nbx, int nblk,
     const int16_t* mv_in, int16_t* mv_out, uint32_t* cost_out) {
   using G = QpelGeom<TB>;
+  constexpr bool SSD = COST == ME_COST_SSD;
   __shared__ QpelLds<TB> s;
   const int b = blockIdx.x, f = blockIdx.y;
   const size_t rec = (size_t)f * nblk + b;
@@ -312,7 +379,7 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_qpel_refine_kernel(
   uint32_t c9[9];
   int ox = 0, oy = 0;  // quarter offset of the best candidate from 4 * m
   uint32_t best;
-  qpel_costs<TB, SSD, true>(s, P, cc, 0, 0, 2, c9);
+  qpel_costs<TB, COST, true>(s, P, cc, 0, 0, 2, c9);
   best = c9[4];
 #pragma unroll
   for (int n = 0; n < 9; n++) {
@@ -323,7 +390,7 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_qpel_refine_kernel(
     }
   }
   const int cx = ox, cy = oy;
-  qpel_costs<TB, SSD, false>(s, P, cc, cx, cy, 1, c9);
+  qpel_costs<TB, COST, false>(s, P, cc, cx, cy, 1, c9);
 #pragma unroll
   for (int n = 0; n < 9; n++) {
     if (n != 4 && c9[n] < best) {
@@ -345,13 +412,14 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_qpel_refine_kernel(
 // centre and strict <.  A kernel of its own, so the plain refinement's code and
 // registers stay as they are.  pred null: all zero; cost_out (Jq) and dist_out
 // (the cost at the result) may be null.
-template <int TB, bool SSD>
+template <int TB, int COST>
 __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_qpel_refine_rd_kernel(
     const uint8_t* __restrict__ ref, size_t ref_frame_stride, const uint8_t* __restrict__ cur,
     size_t cur_frame_stride, int width, int height, int stride, int blk, int nbx, int nblk,
     uint32_t lambda, const int16_t* pred, const int16_t* mv_in, int16_t* mv_out,
     uint32_t* cost_out, uint32_t* dist_out) {
   using G = QpelGeom<TB>;
+  constexpr bool SSD = COST == ME_COST_SSD;
   __shared__ QpelLds<TB> s;
   const int b = blockIdx.x, f = blockIdx.y;
   const size_t rec = (size_t)f * nblk + b;
@@ -378,7 +446,7 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_qpel_refine_rd_kernel(
   };
   uint32_t c9[9];
   int ox = 0, oy = 0;  // quarter offset of the best candidate from 4 * m
-  qpel_costs<TB, SSD, true>(s, P, cc, 0, 0, 2, c9);
+  qpel_costs<TB, COST, true>(s, P, cc, 0, 0, 2, c9);
   uint32_t dist = c9[4], best = dist + rate(0, 0);
 #pragma unroll
   for (int n = 0; n < 9; n++) {
@@ -391,7 +459,7 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_qpel_refine_rd_kernel(
     }
   }
   const int cx = ox, cy = oy;
-  qpel_costs<TB, SSD, false>(s, P, cc, cx, cy, 1, c9);
+  qpel_costs<TB, COST, false>(s, P, cc, cx, cy, 1, c9);
 #pragma unroll
   for (int n = 0; n < 9; n++) {
     if (n == 4) continue;
@@ -481,9 +549,11 @@ struct BipredLds : QpelLds<TB> {
 };
 
 // Adds the cost terms of 4 (masked) prediction bytes p against cur bytes c.
-template <bool SSD>
+template <int TB, int COST>
 __device__ __forceinline__ void cost4(uint32_t p, uint32_t c, uint32_t& pp, uint32_t& pc) {
-  if (SSD) {
+  if (COST == ME_COST_SATD) {
+    pp += satd4<TB>(p, c);
+  } else if (COST == ME_COST_SSD) {
     pp = __builtin_amdgcn_udot4(p, p, pp, false);
     pc = __builtin_amdgcn_udot4(p, c, pc, false);
   } else {
@@ -516,12 +586,13 @@ __device__ __forceinline__ void block_sums(QpelLds<TB>& s, uint32_t (&v)[N]) {
 // (cx, cy) on the half grid hg, each averaged with the other reference's
 // prediction held in registers, in raster order; a candidate replaces
 // (best, bx, by) only with a strictly smaller cost.
-template <int TB, bool SSD>
+template <int TB, int COST>
 __device__ __forceinline__ void bipred_pass(QpelLds<TB>& s, const QpelPix<TB>& P, uint32_t cc,
                                             const uint32_t (&held)[QpelGeom<TB>::GPL],
                                             const uint8_t* hg, int cx, int cy, uint32_t& best,
                                             int& bx, int& by) {
   using G = QpelGeom<TB>;
+  constexpr bool SSD = COST == ME_COST_SSD;
   uint32_t v[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) {
@@ -531,7 +602,7 @@ __device__ __forceinline__ void bipred_pass(QpelLds<TB>& s, const QpelPix<TB>& P
 #pragma unroll
     for (int k = 0; k < G::GPL; k++) {
       const uint32_t p = avg4(held[k], qpel_pred4<TB>(hg, P.px0[k], P.py[k], t)) & P.mask[k];
-      cost4<SSD>(p, P.cur[k], pp, pc);
+      cost4<TB, COST>(p, P.cur[k], pp, pc);
     }
     v[j] = SSD ? pp + cc - 2 * pc : pp;
   }
@@ -550,7 +621,7 @@ __device__ __forceinline__ void bipred_pass(QpelLds<TB>& s, const QpelPix<TB>& P
 // One block (workgroup) per macroblock, the frame in blockIdx.y.  The outputs
 // may be the inputs: a block reads its own records before its first barrier
 // and writes them after its last.
-template <int TB, bool SSD>
+template <int TB, int COST>
 __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_bipred_kernel(
     const uint8_t* __restrict__ ref0, size_t ref0_frame_stride, const uint8_t* __restrict__ ref1,
     size_t ref1_frame_stride, const uint8_t* __restrict__ cur, size_t cur_frame_stride, int width,
@@ -558,6 +629,7 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_bipred_kernel(
     const int16_t* q1_in, int16_t* q0_out, int16_t* q1_out, uint8_t* mode_out, uint32_t* cost_out,
     uint32_t* cost3_out) {
   using G = QpelGeom<TB>;
+  constexpr bool SSD = COST == ME_COST_SSD;
   __shared__ BipredLds<TB> s;
   const int b = blockIdx.x, f = blockIdx.y;
   const size_t rec = (size_t)f * nblk + b;
@@ -597,20 +669,20 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_bipred_kernel(
       const uint32_t a = qpel_pred4<TB>(s.hg, P.px0[k], P.py[k], t0);
       const uint32_t c = qpel_pred4<TB>(s.hg1, P.px0[k], P.py[k], t1);
       held[k] = a;
-      cost4<SSD>(a & P.mask[k], P.cur[k], pp[0], pc[0]);
-      cost4<SSD>(c & P.mask[k], P.cur[k], pp[1], pc[1]);
-      cost4<SSD>(avg4(a, c) & P.mask[k], P.cur[k], pp[2], pc[2]);
+      cost4<TB, COST>(a & P.mask[k], P.cur[k], pp[0], pc[0]);
+      cost4<TB, COST>(c & P.mask[k], P.cur[k], pp[1], pc[1]);
+      cost4<TB, COST>(avg4(a, c) & P.mask[k], P.cur[k], pp[2], pc[2]);
     }
 #pragma unroll
     for (int n = 0; n < 3; n++) c3[n] = SSD ? pp[n] + cc - 2 * pc[n] : pp[n];
     block_sums<TB, 3>(s, c3);
   }
   if (refine) {  // uniform over the grid
-    bipred_pass<TB, SSD>(s, P, cc, held, s.hg1, o1x, o1y, c3[2], o1x, o1y);
+    bipred_pass<TB, COST>(s, P, cc, held, s.hg1, o1x, o1y, c3[2], o1x, o1y);
     const QpelTaps t1 = qpel_taps(o1x, o1y);
 #pragma unroll
     for (int k = 0; k < G::GPL; k++) held[k] = qpel_pred4<TB>(s.hg1, P.px0[k], P.py[k], t1);
-    bipred_pass<TB, SSD>(s, P, cc, held, s.hg, o0x, o0y, c3[2], o0x, o0y);
+    bipred_pass<TB, COST>(s, P, cc, held, s.hg, o0x, o0y, c3[2], o0x, o0y);
   }
   if (threadIdx.x == 0) {
     // L0, L1, BI in that order, a later mode only with a strictly smaller cost
@@ -713,47 +785,54 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_bipred_compensate_kernel(
 
 int tile_of(int blk) { return blk <= 4 ? 4 : blk <= 8 ? 8 : blk <= 16 ? 16 : blk <= 32 ? 32 : 64; }
 
+// cost: ME_COST_SSD, ME_COST_SAD or ME_COST_SATD (the callers reject the rest).
 template <int TB>
-void refine_tb(bool ssd, dim3 grid, hipStream_t stream, const uint8_t* ref, size_t rfs,
+void refine_tb(int cost, dim3 grid, hipStream_t stream, const uint8_t* ref, size_t rfs,
                const uint8_t* cur, size_t cfs, int width, int height, int stride, int blk, int nbx,
                int nblk, const int16_t* mv_in, int16_t* mv_out, uint32_t* cost_out) {
-  if (ssd)
-    hipLaunchKernelGGL((me_qpel_refine_kernel<TB, true>), grid, dim3(QpelGeom<TB>::NT), 0, stream,
-                       ref, rfs, cur, cfs, width, height, stride, blk, nbx, nblk, mv_in, mv_out,
-                       cost_out);
+#define ME_QPEL_REFINE_K(COST)                                                                  \
+  hipLaunchKernelGGL((me_qpel_refine_kernel<TB, COST>), grid, dim3(QpelGeom<TB>::NT), 0, stream, \
+                     ref, rfs, cur, cfs, width, height, stride, blk, nbx, nblk, mv_in, mv_out,  \
+                     cost_out)
+  if (cost == ME_COST_SSD)
+    ME_QPEL_REFINE_K(ME_COST_SSD);
+  else if (cost == ME_COST_SATD)
+    ME_QPEL_REFINE_K(ME_COST_SATD);
   else
-    hipLaunchKernelGGL((me_qpel_refine_kernel<TB, false>), grid, dim3(QpelGeom<TB>::NT), 0, stream,
-                       ref, rfs, cur, cfs, width, height, stride, blk, nbx, nblk, mv_in, mv_out,
-                       cost_out);
+    ME_QPEL_REFINE_K(ME_COST_SAD);
+#undef ME_QPEL_REFINE_K
 }
 
 template <int TB>
-void refine_rd_tb(bool ssd, dim3 grid, hipStream_t stream, const uint8_t* ref, size_t rfs,
+void refine_rd_tb(int cost, dim3 grid, hipStream_t stream, const uint8_t* ref, size_t rfs,
                   const uint8_t* cur, size_t cfs, int width, int height, int stride, int blk,
                   int nbx, int nblk, uint32_t lambda, const int16_t* pred, const int16_t* mv_in,
                   int16_t* mv_out, uint32_t* cost_out, uint32_t* dist_out) {
-  if (ssd)
-    hipLaunchKernelGGL((me_qpel_refine_rd_kernel<TB, true>), grid, dim3(QpelGeom<TB>::NT), 0,
-                       stream, ref, rfs, cur, cfs, width, height, stride, blk, nbx, nblk, lambda,
-                       pred, mv_in, mv_out, cost_out, dist_out);
+#define ME_QPEL_REFINE_RD_K(COST)                                                               \
+  hipLaunchKernelGGL((me_qpel_refine_rd_kernel<TB, COST>), grid, dim3(QpelGeom<TB>::NT), 0,     \
+                     stream, ref, rfs, cur, cfs, width, height, stride, blk, nbx, nblk, lambda, \
+                     pred, mv_in, mv_out, cost_out, dist_out)
+  if (cost == ME_COST_SSD)
+    ME_QPEL_REFINE_RD_K(ME_COST_SSD);
+  else if (cost == ME_COST_SATD)
+    ME_QPEL_REFINE_RD_K(ME_COST_SATD);
   else
-    hipLaunchKernelGGL((me_qpel_refine_rd_kernel<TB, false>), grid, dim3(QpelGeom<TB>::NT), 0,
-                       stream, ref, rfs, cur, cfs, width, height, stride, blk, nbx, nblk, lambda,
-                       pred, mv_in, mv_out, cost_out, dist_out);
+    ME_QPEL_REFINE_RD_K(ME_COST_SAD);
+#undef ME_QPEL_REFINE_RD_K
 }
 
 }  // namespace
 
 hipError_t launch_qpel_refine_rd(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
                                  size_t cur_frame_stride, int width, int height, int stride,
-                                 int blk, bool ssd, uint32_t lambda, int n_frames,
+                                 int blk, int cost, uint32_t lambda, int n_frames,
                                  const int16_t* pred, const int16_t* mv_in, int16_t* mv_out,
                                  uint32_t* cost_out, uint32_t* dist_out, hipStream_t stream) {
   const int nbx = (width + blk - 1) / blk, nblk = nbx * ((height + blk - 1) / blk);
   const dim3 grid((unsigned)nblk, (unsigned)n_frames);
 #define ME_QPEL_REFINE_RD(TB)                                                                   \
   case TB:                                                                                      \
-    refine_rd_tb<TB>(ssd, grid, stream, ref, ref_frame_stride, cur, cur_frame_stride, width,    \
+    refine_rd_tb<TB>(cost, grid, stream, ref, ref_frame_stride, cur, cur_frame_stride, width,   \
                      height, stride, blk, nbx, nblk, lambda, pred, mv_in, mv_out, cost_out,     \
                      dist_out);                                                                 \
     break
@@ -770,13 +849,13 @@ hipError_t launch_qpel_refine_rd(const uint8_t* ref, size_t ref_frame_stride, co
 
 hipError_t launch_qpel_refine(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
                               size_t cur_frame_stride, int width, int height, int stride, int blk,
-                              bool ssd, int n_frames, const int16_t* mv_in, int16_t* mv_out,
+                              int cost, int n_frames, const int16_t* mv_in, int16_t* mv_out,
                               uint32_t* cost_out, hipStream_t stream) {
   const int nbx = (width + blk - 1) / blk, nblk = nbx * ((height + blk - 1) / blk);
   const dim3 grid((unsigned)nblk, (unsigned)n_frames);
 #define ME_QPEL_REFINE(TB)                                                                      \
   case TB:                                                                                      \
-    refine_tb<TB>(ssd, grid, stream, ref, ref_frame_stride, cur, cur_frame_stride, width,       \
+    refine_tb<TB>(cost, grid, stream, ref, ref_frame_stride, cur, cur_frame_stride, width,      \
                   height, stride, blk, nbx, nblk, mv_in, mv_out, cost_out);                     \
     break
   switch (tile_of(blk)) {
@@ -813,23 +892,25 @@ hipError_t launch_qpel_compensate(const uint8_t* ref, const uint8_t* cur, int wi
 
 hipError_t launch_bipred(const uint8_t* ref0, size_t ref0_frame_stride, const uint8_t* ref1,
                          size_t ref1_frame_stride, const uint8_t* cur, size_t cur_frame_stride,
-                         int width, int height, int stride, int blk, bool ssd, int refine,
+                         int width, int height, int stride, int blk, int cost, int refine,
                          int n_frames, const int16_t* q0_in, const int16_t* q1_in, int16_t* q0_out,
                          int16_t* q1_out, uint8_t* mode_out, uint32_t* cost_out,
                          uint32_t* cost3_out, hipStream_t stream) {
   const int nbx = (width + blk - 1) / blk, nblk = nbx * ((height + blk - 1) / blk);
   const dim3 grid((unsigned)nblk, (unsigned)n_frames);
-#define ME_BIPRED_K(TB, SSD)                                                                    \
-  hipLaunchKernelGGL((me_bipred_kernel<TB, SSD>), grid, dim3(QpelGeom<TB>::NT), 0, stream, ref0, \
-                     ref0_frame_stride, ref1, ref1_frame_stride, cur, cur_frame_stride, width,  \
-                     height, stride, blk, nbx, nblk, refine, q0_in, q1_in, q0_out, q1_out,      \
-                     mode_out, cost_out, cost3_out)
-#define ME_BIPRED(TB)                \
-  case TB:                           \
-    if (ssd)                         \
-      ME_BIPRED_K(TB, true);         \
-    else                             \
-      ME_BIPRED_K(TB, false);        \
+#define ME_BIPRED_K(TB, COST)                                                                   \
+  hipLaunchKernelGGL((me_bipred_kernel<TB, COST>), grid, dim3(QpelGeom<TB>::NT), 0, stream,     \
+                     ref0, ref0_frame_stride, ref1, ref1_frame_stride, cur, cur_frame_stride,   \
+                     width, height, stride, blk, nbx, nblk, refine, q0_in, q1_in, q0_out,       \
+                     q1_out, mode_out, cost_out, cost3_out)
+#define ME_BIPRED(TB)                  \
+  case TB:                             \
+    if (cost == ME_COST_SSD)           \
+      ME_BIPRED_K(TB, ME_COST_SSD);    \
+    else if (cost == ME_COST_SATD)     \
+      ME_BIPRED_K(TB, ME_COST_SATD);   \
+    else                               \
+      ME_BIPRED_K(TB, ME_COST_SAD);    \
     break
   switch (tile_of(blk)) {
     ME_BIPRED(4);

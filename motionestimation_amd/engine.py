@@ -13,10 +13,14 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import ME_COST_SAD, ME_COST_SSD, ME_COST_SSIM, MEError, check
+from ._lib import ME_COST_SAD, ME_COST_SATD, ME_COST_SSD, ME_COST_SSIM, MEError, check
 
+# "satd": the quarter-pel refinements, the bi-prediction and their composites
+# (include/me.h "SATD cost"); every integer search rejects it
 _COST = {"ssd": ME_COST_SSD, "mse": ME_COST_SSD, "sad": ME_COST_SAD, "ssim": ME_COST_SSIM,
-         ME_COST_SSD: ME_COST_SSD, ME_COST_SAD: ME_COST_SAD, ME_COST_SSIM: ME_COST_SSIM}
+         "satd": ME_COST_SATD,
+         ME_COST_SSD: ME_COST_SSD, ME_COST_SAD: ME_COST_SAD, ME_COST_SSIM: ME_COST_SSIM,
+         ME_COST_SATD: ME_COST_SATD}
 
 
 def cost_code(cost) -> int:
@@ -331,8 +335,9 @@ class Engine:
 
     # ---- quarter-pel (include/me.h "quarter-pel refinement") ----
     def refine_qpel(self, ref, cur, blk: int, mv, cost="ssd", stride=None):
-        """Refine the integer field mv [nblocks, 2] to quarter-pel.  Returns
-        (mv_q int16 [nblocks, 2], four units per pixel, cost uint32 [nblocks])."""
+        """Refine the integer field mv [nblocks, 2] to quarter-pel on cost
+        "ssd", "sad" or "satd".  Returns (mv_q int16 [nblocks, 2], four units
+        per pixel, cost uint32 [nblocks])."""
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         cur = np.ascontiguousarray(cur, dtype=np.uint8)
         if ref.ndim != 2 or ref.shape != cur.shape:
@@ -349,7 +354,8 @@ class Engine:
         return q[:n], cst[:n]
 
     def full_search_qpel(self, ref, cur, blk: int, span: int, cost="ssd", stride=None):
-        """full_search and refine_qpel back to back on the device.  Returns
+        """full_search and refine_qpel back to back on the device ("satd": the
+        search at SAD, the refinement at SATD).  Returns
         (mv_q int16 [nblocks, 2] in quarter-pel units, cost uint32 [nblocks])."""
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         cur = np.ascontiguousarray(cur, dtype=np.uint8)

@@ -93,6 +93,9 @@ def main():
         "refine_share_of_search": round(refine_us / search_us, 3),
         "search_us_per_frame_min": round(min(ms["search"]) * 1e3 / F, 2),
         "search_refine_us_per_frame_min": round(min(ms["search_refine"]) * 1e3 / F, 2),
+        # the spread of the steps, for an A/B of two builds
+        "search_refine_us_per_frame_p10_p90": [
+            round(sorted(ms["search_refine"])[int(p * a.steps)] * 1e3 / F, 2) for p in (0.1, 0.9)],
         "refine_hbm_bytes_per_frame": hbm,
         "refine_hbm_gb_per_s": round(hbm / (refine_us * 1e-6) / 1e9, 1) if refine_us > 0 else None,
         "frame0_equals_oracle": ok, "frame0_fractional_blocks": round(frac, 3),
