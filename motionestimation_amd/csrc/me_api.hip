@@ -6,7 +6,6 @@
 // records to the first device).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
-#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,8 +18,6 @@
 #include <vector>
 
 #include "me_internal.h"
-#include "me_partition.h"
-#include "me_rd.h"
 
 using me::Dev;
 
@@ -180,33 +177,6 @@ me_status grow(me_ctx* c, void** p, size_t* cap, size_t need) {
   return ME_OK;
 }
 
-// SATD costs sub-pel candidates only: the quarter-pel refinements and the
-// bi-prediction take it, their composite entry points search at SAD first
-// (search_cost), and an integer search asked for it is a valid request this
-// build does not serve.
-static const char SATD_NO_SEARCH[] =
-    "integer searches have no SATD cost (quarter-pel refinement and bi-prediction only)";
-static me_cost search_cost(me_cost cost) { return cost == ME_COST_SATD ? ME_COST_SAD : cost; }
-
-me_status check_args(me_ctx* c, const void* ref, const void* cur, int width, int height,
-                     int stride, int blk, int range, int cost, const void* mv) {
-  if (!c) return ME_EINVAL;
-  if (!ref || !cur || !mv) return fail(c, ME_EINVAL, "null plane or output pointer");
-  if (width <= 0 || height <= 0) return fail(c, ME_EINVAL, "frame %dx%d", width, height);
-  if (stride < width) return fail(c, ME_EINVAL, "stride %d < width %d", stride, width);
-  if (blk < 1 || blk > ME_MAX_BLOCK) return fail(c, ME_EINVAL, "block_size %d", blk);
-  if (range < 0 || range > ME_MAX_RANGE) return fail(c, ME_EINVAL, "search_range %d", range);
-  if (cost != ME_COST_SSD && cost != ME_COST_SAD && cost != ME_COST_SSIM && cost != ME_COST_SATD)
-    return fail(c, ME_EINVAL, "cost %d", cost);
-  // (the sub-pel entry points pass search_cost(cost): SATD never arrives from them)
-  if (cost == ME_COST_SATD) return fail(c, ME_EUNSUPPORTED, "%s", SATD_NO_SEARCH);
-  // Buffer descriptors carry 32-bit byte ranges: planes stay below 2 GiB.
-  if ((long long)stride * height >= (1LL << 31))
-    return fail(c, ME_EUNSUPPORTED, "plane of %lld bytes (limit 2 GiB)",
-                (long long)stride * height);
-  return ME_OK;
-}
-
 SearchArgs make_args(const SearchJob& J, int width, int height, int stride, int blk, int range,
                      int cost) {
   SearchArgs p{};  // (no context buffers yet: attach_scratch)
@@ -218,19 +188,6 @@ SearchArgs make_args(const SearchJob& J, int width, int height, int stride, int 
   p.nbx = (width + blk - 1) / blk;
   p.cost_kind = cost;
   return job_args(p, J);
-}
-
-me_status check_stripe(me_ctx* c, int nby, int blk, int range, int r0, int r1, int ref_row0,
-                       int cur_row0, int job) {
-  const int need_ref0 = r0 * blk - range > 0 ? r0 * blk - range : 0;
-  const bool rows = r0 < 0 || r1 > nby || r0 > r1;
-  const bool ref = ref_row0 < 0 || ref_row0 > need_ref0, cur = cur_row0 < 0 || cur_row0 > r0 * blk;
-  if (!rows && !ref && !cur) return ME_OK;
-  char pre[24] = "";
-  if (job >= 0) snprintf(pre, sizeof pre, "job %d: ", job);
-  if (rows) return fail(c, ME_EINVAL, "%sblock rows [%d, %d)", pre, r0, r1);
-  if (ref) return fail(c, ME_EINVAL, "%sref_row0 %d", pre, ref_row0);
-  return fail(c, ME_EINVAL, "%scur_row0 %d", pre, cur_row0);
 }
 
 me_status attach_scratch(me_ctx* c, Dev& d, SearchArgs& p, bool cap, int batch, const SearchJob* jobs,
@@ -325,6 +282,23 @@ me_status launch_ordered(me_ctx* c, Dev& d, const SearchArgs& base, const Search
 
 me_status own_stream(me_ctx* c, Dev& d) {
   if (!d.stream) HIPCHK(c, hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+  return ME_OK;
+}
+
+me_status upload_planes(me_ctx* c, Dev& d, std::initializer_list<const uint8_t*> planes, int width,
+                        int height, int stride, size_t rec_bytes) {
+  HIPCHK(c, hipSetDevice(d.id));
+  me_status s = own_stream(c, d);
+  if (s != ME_OK) return s;
+  const size_t plane = (size_t)width * height;
+  if ((s = grow(c, (void**)&d.ref, &d.frame_cap, planes.size() * plane)) != ME_OK) return s;
+  d.cur = d.ref + plane;
+  if ((s = grow(c, (void**)&d.rec, &d.rec_cap, rec_bytes)) != ME_OK) return s;
+  uint8_t* to = d.ref;
+  for (const uint8_t* from : planes) {
+    HIPCHK(c, hipMemcpy2DAsync(to, width, from, stride, width, height, hipMemcpyHostToDevice, d.stream));
+    to += plane;
+  }
   return ME_OK;
 }
 
@@ -456,7 +430,6 @@ namespace {
 using me::fail;
 using me::grow;
 using me::check_args;
-using me::search_cost;
 using me::make_args;
 using me::attach_scratch;
 using me::launch_ordered;
@@ -495,14 +468,15 @@ me_status stripe_upload_launch(me_ctx* c, Dev& d, const uint8_t* ref, const uint
   if ((s = grow(c, (void**)&d.ref, &d.frame_cap, (ref_rows + cur_rows + 1) * width)) != ME_OK)
     return s;
   d.cur = d.ref + ref_rows * width;
-  if ((s = grow(c, (void**)&d.rec, &d.rec_cap, max_blocks * 8)) != ME_OK) return s;
+  const me::rules::Layout L = me::rules::layout_mv_cost(max_blocks);
+  if ((s = grow(c, (void**)&d.rec, &d.rec_cap, L.total)) != ME_OK) return s;
   if (r1 <= r0) return ME_OK;
   HIPCHK(c, hipMemcpy2DAsync(d.ref, width, ref + (size_t)y_ref0 * stride, stride, width,
                              ref_rows, hipMemcpyHostToDevice, d.stream));
   HIPCHK(c, hipMemcpy2DAsync(d.cur, width, cur + (size_t)y_cur0 * stride, stride, width,
                              cur_rows, hipMemcpyHostToDevice, d.stream));
-  int16_t* dmv = reinterpret_cast<int16_t*>(d.rec);
-  uint32_t* dcost = reinterpret_cast<uint32_t*>(d.rec + max_blocks * 4);
+  int16_t* dmv = me::rec_at<int16_t>(d, L, me::rules::REC_MV);
+  uint32_t* dcost = me::rec_at<uint32_t>(d, L, me::rules::REC_COST);
   const me::SearchJob J{d.ref, y_ref0, d.cur, y_cur0, r0, r1, dmv, dcost};
   me::SearchArgs p = make_args(J, width, height, width, blk, range, cost);
   if ((s = attach_scratch(c, d, p)) != ME_OK) return s;
@@ -526,7 +500,8 @@ me_status multi_search(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int wi
   for (int i = 0; i < n; i++)
     max_rows = bounds[i + 1] - bounds[i] > max_rows ? bounds[i + 1] - bounds[i] : max_rows;
   const size_t max_blocks = (size_t)(max_rows > 0 ? max_rows : 1) * nbx;
-  const size_t rec_bytes = max_blocks * 8;
+  const me::rules::Layout L = me::rules::layout_mv_cost(max_blocks);  // each stripe's records
+  const size_t rec_bytes = L.total;
 
   {
     // one persistent host thread per device (me::Workers), not threads per call
@@ -615,8 +590,8 @@ me_status multi_search(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int wi
     const int nblk = (bounds[i + 1] - bounds[i]) * nbx;
     const uint8_t* base = host.data() + i * rec_bytes;
     const size_t off = (size_t)bounds[i] * nbx;
-    memcpy(mv_xy + 2 * off, base, (size_t)nblk * 4);
-    if (block_cost) memcpy(block_cost + off, base + max_blocks * 4, (size_t)nblk * 4);
+    memcpy(mv_xy + 2 * off, base + L.off[me::rules::REC_MV], (size_t)nblk * 4);
+    if (block_cost) memcpy(block_cost + off, base + L.off[me::rules::REC_COST], (size_t)nblk * 4);
   }
   return ME_OK;
 }
@@ -922,17 +897,11 @@ me_status me_full_search(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int 
   if (c->devs.size() > 1)
     return multi_search(c, ref, cur, width, height, stride, blk, range, cost, mv_xy, block_cost);
   Dev& d = c->devs[0];
-  HIPCHK(c, hipSetDevice(d.id));
-  if ((s = me::own_stream(c, d)) != ME_OK) return s;
-  const size_t plane = (size_t)width * height;
   const size_t nb = (size_t)me_num_blocks(width, height, blk);
-  if ((s = grow(c, (void**)&d.ref, &d.frame_cap, 2 * plane)) != ME_OK) return s;
-  d.cur = d.ref + plane;
-  if ((s = grow(c, (void**)&d.rec, &d.rec_cap, nb * 8)) != ME_OK) return s;
-  HIPCHK(c, hipMemcpy2DAsync(d.ref, width, ref, stride, width, height, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(c, hipMemcpy2DAsync(d.cur, width, cur, stride, width, height, hipMemcpyHostToDevice, d.stream));
-  int16_t* dmv = reinterpret_cast<int16_t*>(d.rec);
-  uint32_t* dcost = reinterpret_cast<uint32_t*>(d.rec + nb * 4);
+  const me::rules::Layout L = me::rules::layout_mv_cost(nb);
+  if ((s = me::upload_planes(c, d, {ref, cur}, width, height, stride, L.total)) != ME_OK) return s;
+  int16_t* dmv = me::rec_at<int16_t>(d, L, me::rules::REC_MV);
+  uint32_t* dcost = me::rec_at<uint32_t>(d, L, me::rules::REC_COST);
   const int nby = (height + blk - 1) / blk;
   const me::SearchJob J{d.ref, 0, d.cur, 0, 0, nby, dmv, dcost};
   me::SearchArgs p = make_args(J, width, height, width, blk, range, cost);
@@ -1010,8 +979,9 @@ me_status me_full_search_batch_device(me_ctx* c, const uint8_t* d_ref, size_t re
                                      int range, me_cost cost, int r0, int r1, int n_frames,
                                      int16_t* d_mv, uint32_t* d_cost, void* stream) {
   if (!c) return ME_EINVAL;
-  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
-  me_status s = check_args(c, d_ref, d_cur, width, height, stride, blk, range, cost, d_mv);
+  me_status s = me::rules::frame_batch(n_frames, nullptr, 0, c->err, sizeof c->err);
+  if (s != ME_OK) return s;
+  s = check_args(c, d_ref, d_cur, width, height, stride, blk, range, cost, d_mv);
   if (s != ME_OK) return s;
   const int nby = (height + blk - 1) / blk;
   // (the rows only: the frames' ref_row0 / cur_row0 are reported per job below)
@@ -1019,16 +989,9 @@ me_status me_full_search_batch_device(me_ctx* c, const uint8_t* d_ref, size_t re
   // every frame's resident rows inside its stride (frames must not overlap)
   const me::SearchArgs p = make_args(me::SearchJob{d_ref, ref_row0, d_cur, cur_row0, r0, r1, d_mv, d_cost},
                                      width, height, stride, blk, range, cost);
-  if (n_frames > 1 && (ref_frame_stride < p.ref_bytes || cur_frame_stride < p.cur_bytes))
-    return fail(c, ME_EINVAL, "frame strides %zu / %zu below a frame's %u / %u bytes",
-                ref_frame_stride, cur_frame_stride, p.ref_bytes, p.cur_bytes);
-  // One plane stack per batch, below 2 GiB like a single plane (check_args):
-  // a stride past it is a caller error, refused before any frame address is
-  // formed (a wild stride would otherwise send the kernels to unmapped memory).
-  const unsigned long long rb = (unsigned long long)(n_frames - 1) * ref_frame_stride + p.ref_bytes;
-  const unsigned long long cb = (unsigned long long)(n_frames - 1) * cur_frame_stride + p.cur_bytes;
-  if (rb >= (1ull << 31) || cb >= (1ull << 31))
-    return fail(c, ME_EUNSUPPORTED, "batch of %llu / %llu bytes (limit 2 GiB)", rb, cb);
+  // and the two plane stacks below 2 GiB like a single plane (check_args)
+  const me::rules::FramePlane fp[2] = {{ref_frame_stride, p.ref_bytes}, {cur_frame_stride, p.cur_bytes}};
+  if ((s = me::rules::frame_batch(n_frames, fp, 2, c->err, sizeof c->err)) != ME_OK) return s;
   const size_t nblk = (size_t)(r1 - r0) * ((width + blk - 1) / blk);
   std::vector<me_stripe_job> jobs((size_t)n_frames);
   for (int f = 0; f < n_frames; f++)
@@ -1056,15 +1019,9 @@ me_status me_find_best_blocks(me_ctx* c, const int* ref_frame, const int* cur_fr
   if (num_blks != nb) return fail(c, ME_EINVAL, "num_blks %d != %d", num_blks, nb);
   const size_t plane = (size_t)width * height;
   std::vector<uint8_t> r8(plane), c8(plane);
-  for (size_t i = 0; i < plane; i++) {  // utils.c:49-53 widened u8 -> int; narrow back
-    const int rv = ref_frame[i], cv = cur_frame[i];
-    // the planes came from 8-bit files: anything else would be searched as
-    // its low byte and give a field the reference would not
-    if ((unsigned)rv > 255u || (unsigned)cv > 255u)
-      return fail(c, ME_EINVAL, "pixel %zu (%d, %d) outside [0, 255]", i, rv, cv);
-    r8[i] = (uint8_t)rv;
-    c8[i] = (uint8_t)cv;
-  }
+  // utils.c:49-53 widened u8 -> int: narrowed back while the rule reads them
+  if ((s = me::rules::pixels(ref_frame, cur_frame, plane, r8.data(), c8.data(), c->err, sizeof c->err)) != ME_OK)
+    return s;
   std::vector<int16_t> mv((size_t)nb * 2);
   s = me_full_search(c, r8.data(), c8.data(), width, height, width, blk, range, ME_COST_SSD,
                      mv.data(), nullptr);
@@ -1074,916 +1031,6 @@ me_status me_find_best_blocks(me_ctx* c, const int* ref_frame, const int* cur_fr
     blks[i].motion_vectorY = mv[2 * i + 1];
     blks[i].is_best_match_found = 1;
   }
-  return ME_OK;
-}
-
-static me_status compensate(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
-                            int height, int blk, const int16_t* mv_xy, uint8_t* out,
-                            int planes, double* psnr, bool qpel = false) {
-  me_status s = check_args(c, ref, cur ? cur : ref, width, height, width, blk, 0, ME_COST_SSD, mv_xy);
-  if (s != ME_OK) return s;
-  if (!out) return fail(c, ME_EINVAL, "null output");
-  Dev& d = c->devs[0];
-  HIPCHK(c, hipSetDevice(d.id));
-  if ((s = me::own_stream(c, d)) != ME_OK) return s;
-  const size_t plane = (size_t)width * height;
-  const size_t nb = (size_t)me_num_blocks(width, height, blk);
-  if ((s = grow(c, (void**)&d.ref, &d.frame_cap, 2 * plane)) != ME_OK) return s;
-  d.cur = d.ref + plane;
-  if ((s = grow(c, (void**)&d.rec, &d.rec_cap, nb * 8)) != ME_OK) return s;
-  size_t scap = d.stats ? 16 : 0;
-  if ((s = grow(c, (void**)&d.stats, &scap, 16)) != ME_OK) return s;
-  const size_t out_bytes = planes ? 5 * plane : plane;
-  if ((s = grow(c, (void**)&d.out5, &d.out_cap, out_bytes)) != ME_OK) return s;
-  HIPCHK(c, hipMemcpyAsync(d.ref, ref, plane, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(c, hipMemcpyAsync(d.cur, cur ? cur : ref, plane, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(c, hipMemcpyAsync(d.rec, mv_xy, nb * 4, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(c, hipMemsetAsync(d.stats, 0, 16, d.stream));
-  HIPCHK(c, (qpel ? me::launch_qpel_compensate : me::launch_compensate)(
-                d.ref, d.cur, width, height, blk, reinterpret_cast<int16_t*>(d.rec), d.out5, planes,
-                d.stats, d.stream));
-  unsigned long long st[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(out, d.out5, out_bytes, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipMemcpyAsync(st, d.stats, 16, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipStreamSynchronize(d.stream));
-  if (psnr) {  // utils.c:147-154, double arithmetic on the exact integer sum
-    double mse = (double)st[0];
-    mse /= (double)width * height;
-    *psnr = mse == 0 ? 99.0 : 20 * log10((double)st[1]) - 10 * log10(mse);
-  }
-  return ME_OK;
-}
-
-me_status me_motion_compensate(me_ctx* c, const uint8_t* ref, int width, int height, int blk,
-                               const int16_t* mv_xy, uint8_t* mc) {
-  return compensate(c, ref, nullptr, width, height, blk, mv_xy, mc, 0, nullptr);
-}
-
-me_status me_compensate_planes(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
-                               int height, int blk, const int16_t* mv_xy, uint8_t* out5,
-                               double* psnr) {
-  if (!cur) return fail(c, ME_EINVAL, "null cur");
-  return compensate(c, ref, cur, width, height, blk, mv_xy, out5, 1, psnr);
-}
-
-// ---- quarter-pel refinement and sub-pel compensation (me_subpel.hip) ----
-
-// The refinement's own argument rules on top of check_args.
-static me_status check_qpel(me_ctx* c, me_cost cost, const void* mv_q) {
-  if (!mv_q) return me::fail(c, ME_EINVAL, "null quarter-pel output");
-  if (cost == ME_COST_SSIM)
-    return me::fail(c, ME_EUNSUPPORTED, "quarter-pel refinement has no SSIM cost (SAD, SSD or SATD)");
-  return ME_OK;
-}
-
-// Enqueue the refinement of n_frames frames on s after the device's previous
-// search (not while capturing: me_graph_launch orders the graph).
-static me_status refine_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rfs,
-                           const uint8_t* d_cur, size_t cfs, int width, int height, int stride,
-                           int blk, me_cost cost, int n_frames, const int16_t* d_mv,
-                           int16_t* d_q, uint32_t* d_cost, hipStream_t s) {
-  if (!me::capturing(s)) {
-    me_status st = me::order_on(c, d, s);
-    if (st != ME_OK) return st;
-  }
-  const hipError_t e = me::launch_qpel_refine(d_ref, rfs, d_cur, cfs, width, height, stride, blk,
-                                              cost, n_frames, d_mv, d_q, d_cost, s);
-  if (e != hipSuccess)
-    return me::fail(c, ME_EDEVICE, "quarter-pel refinement launch: %s", hipGetErrorString(e));
-  return ME_OK;
-}
-
-me_status me_refine_qpel_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
-                                const uint8_t* d_cur, size_t cur_frame_stride, int width,
-                                int height, int stride, int blk, me_cost cost, int n_frames,
-                                const int16_t* d_mv_xy, int16_t* d_mv_q, uint32_t* d_block_cost,
-                                void* stream) {
-  if (!c) return ME_EINVAL;
-  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
-  me_status s =
-      check_args(c, d_ref, d_cur, width, height, stride, blk, 0, search_cost(cost), d_mv_xy);
-  if (s != ME_OK) return s;
-  if ((s = check_qpel(c, cost, d_mv_q)) != ME_OK) return s;
-  // frames must not overlap and a plane stack stays below 2 GiB, as in
-  // me_full_search_batch_device
-  const unsigned long long fb = (unsigned long long)stride * height;
-  if (n_frames > 1 && (ref_frame_stride < fb || cur_frame_stride < fb))
-    return fail(c, ME_EINVAL, "frame strides %zu / %zu below a frame's %llu bytes",
-                ref_frame_stride, cur_frame_stride, fb);
-  const unsigned long long rb = (unsigned long long)(n_frames - 1) * ref_frame_stride + fb;
-  const unsigned long long cb = (unsigned long long)(n_frames - 1) * cur_frame_stride + fb;
-  if (rb >= (1ull << 31) || cb >= (1ull << 31))
-    return fail(c, ME_EUNSUPPORTED, "batch of %llu / %llu bytes (limit 2 GiB)", rb, cb);
-  c->err[0] = 0;
-  return refine_on(c, c->devs[0], d_ref, ref_frame_stride, d_cur, cur_frame_stride, width, height,
-                   stride, blk, cost, n_frames, d_mv_xy, d_mv_q, d_block_cost,
-                   (hipStream_t)stream);
-}
-
-// Upload host planes (packed on the device) and size the record buffer:
-// d.ref, d.cur and d.rec = [mv | cost] of nb blocks, on d.stream.
-static me_status upload_pair(me_ctx* c, Dev& d, const uint8_t* ref, const uint8_t* cur, int width,
-                             int height, int stride, size_t nb) {
-  HIPCHK(c, hipSetDevice(d.id));
-  me_status s = me::own_stream(c, d);
-  if (s != ME_OK) return s;
-  const size_t plane = (size_t)width * height;
-  if ((s = grow(c, (void**)&d.ref, &d.frame_cap, 2 * plane)) != ME_OK) return s;
-  d.cur = d.ref + plane;
-  if ((s = grow(c, (void**)&d.rec, &d.rec_cap, nb * 8)) != ME_OK) return s;
-  HIPCHK(c, hipMemcpy2DAsync(d.ref, width, ref, stride, width, height, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(c, hipMemcpy2DAsync(d.cur, width, cur, stride, width, height, hipMemcpyHostToDevice, d.stream));
-  return ME_OK;
-}
-
-me_status me_refine_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width, int height,
-                         int stride, int blk, me_cost cost, const int16_t* mv_xy, int16_t* mv_q,
-                         uint32_t* block_cost) {
-  me_status s = check_args(c, ref, cur, width, height, stride, blk, 0, search_cost(cost), mv_xy);
-  if (s != ME_OK) return s;
-  if ((s = check_qpel(c, cost, mv_q)) != ME_OK) return s;
-  const size_t nb = (size_t)me_num_blocks(width, height, blk);
-  for (size_t i = 0; i < 2 * nb; i++)
-    if (mv_xy[i] > ME_QPEL_MAX_MV || mv_xy[i] < -ME_QPEL_MAX_MV)
-      return fail(c, ME_EINVAL, "block %zu: vector component %d beyond ME_QPEL_MAX_MV (%d)", i / 2,
-                  (int)mv_xy[i], ME_QPEL_MAX_MV);
-  c->err[0] = 0;
-  Dev& d = c->devs[0];
-  if ((s = upload_pair(c, d, ref, cur, width, height, stride, nb)) != ME_OK) return s;
-  int16_t* dmv = reinterpret_cast<int16_t*>(d.rec);
-  uint32_t* dcost = reinterpret_cast<uint32_t*>(d.rec + nb * 4);
-  HIPCHK(c, hipMemcpyAsync(dmv, mv_xy, nb * 4, hipMemcpyHostToDevice, d.stream));
-  if ((s = refine_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, cost, 1, dmv, dmv, dcost,
-                     d.stream)) != ME_OK)
-    return s;
-  HIPCHK(c, hipMemcpyAsync(mv_q, dmv, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  if (block_cost)
-    HIPCHK(c, hipMemcpyAsync(block_cost, dcost, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipStreamSynchronize(d.stream));
-  return ME_OK;
-}
-
-me_status me_full_search_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
-                              int height, int stride, int blk, int range, me_cost cost,
-                              int16_t* mv_q, uint32_t* block_cost) {
-  me_status s =
-      check_args(c, ref, cur, width, height, stride, blk, range, search_cost(cost), mv_q);
-  if (s != ME_OK) return s;
-  if ((s = check_qpel(c, cost, mv_q)) != ME_OK) return s;
-  if (c->devs.size() > 1)
-    return fail(c, ME_EUNSUPPORTED, "quarter-pel search on %zu devices (one device only)",
-                c->devs.size());
-  c->err[0] = 0;
-  Dev& d = c->devs[0];
-  const size_t nb = (size_t)me_num_blocks(width, height, blk);
-  if ((s = upload_pair(c, d, ref, cur, width, height, stride, nb)) != ME_OK) return s;
-  int16_t* dmv = reinterpret_cast<int16_t*>(d.rec);
-  uint32_t* dcost = reinterpret_cast<uint32_t*>(d.rec + nb * 4);
-  const int nby = (height + blk - 1) / blk;
-  const me::SearchJob J{d.ref, 0, d.cur, 0, 0, nby, dmv, dcost};
-  // (SATD: the integer search runs at SAD)
-  me::SearchArgs p = make_args(J, width, height, width, blk, range, search_cost(cost));
-  if ((s = attach_scratch(c, d, p)) != ME_OK) return s;
-  if ((s = launch_ordered(c, d, p, &J, 1, d.stream)) != ME_OK) return s;
-  // the searched vectors stay inside the window (|m| <= ME_MAX_RANGE): refine in place
-  if ((s = refine_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, cost, 1, dmv, dmv, dcost,
-                     d.stream)) != ME_OK)
-    return s;
-  HIPCHK(c, hipMemcpyAsync(mv_q, dmv, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  if (block_cost)
-    HIPCHK(c, hipMemcpyAsync(block_cost, dcost, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  return me::device_status(c, d, d.stream);
-}
-
-me_status me_motion_compensate_qpel(me_ctx* c, const uint8_t* ref, int width, int height, int blk,
-                                    const int16_t* mv_q, uint8_t* mc) {
-  return compensate(c, ref, nullptr, width, height, blk, mv_q, mc, 0, nullptr, true);
-}
-
-me_status me_compensate_planes_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
-                                    int height, int blk, const int16_t* mv_q, uint8_t* out5,
-                                    double* psnr) {
-  if (!cur) return fail(c, ME_EINVAL, "null cur");
-  return compensate(c, ref, cur, width, height, blk, mv_q, out5, 1, psnr, true);
-}
-
-// ---- bi-prediction (me_subpel.hip) ----
-
-static me_status check_bipred(me_ctx* c, me_cost cost, const void* ref1, const void* q1,
-                              const void* out0, const void* out1, const void* mode) {
-  if (!ref1 || !q1 || !out0 || !out1 || !mode)
-    return me::fail(c, ME_EINVAL, "null bi-prediction plane, field or mode pointer");
-  if (cost == ME_COST_SSIM)
-    return me::fail(c, ME_EUNSUPPORTED, "bi-prediction has no SSIM cost (SAD, SSD or SATD)");
-  return ME_OK;
-}
-
-// Enqueue the bi-prediction of n_frames frames on s after the device's
-// previous search (not while capturing: me_graph_launch orders the graph).
-static me_status bipred_on(me_ctx* c, Dev& d, const uint8_t* d_ref0, size_t r0fs,
-                           const uint8_t* d_ref1, size_t r1fs, const uint8_t* d_cur, size_t cfs,
-                           int width, int height, int stride, int blk, me_cost cost, int refine,
-                           int n_frames, const int16_t* q0, const int16_t* q1, int16_t* out0,
-                           int16_t* out1, uint8_t* mode, uint32_t* d_cost, uint32_t* d_cost3,
-                           hipStream_t s) {
-  if (!me::capturing(s)) {
-    me_status st = me::order_on(c, d, s);
-    if (st != ME_OK) return st;
-  }
-  const hipError_t e = me::launch_bipred(d_ref0, r0fs, d_ref1, r1fs, d_cur, cfs, width, height,
-                                         stride, blk, cost, refine, n_frames, q0, q1,
-                                         out0, out1, mode, d_cost, d_cost3, s);
-  if (e != hipSuccess)
-    return me::fail(c, ME_EDEVICE, "bi-prediction launch: %s", hipGetErrorString(e));
-  return ME_OK;
-}
-
-me_status me_bipred_device(me_ctx* c, const uint8_t* d_ref0, size_t ref0_frame_stride,
-                           const uint8_t* d_ref1, size_t ref1_frame_stride, const uint8_t* d_cur,
-                           size_t cur_frame_stride, int width, int height, int stride, int blk,
-                           me_cost cost, int refine, int n_frames, const int16_t* d_mv_q0,
-                           const int16_t* d_mv_q1, int16_t* d_mv_out0, int16_t* d_mv_out1,
-                           uint8_t* d_mode, uint32_t* d_block_cost, uint32_t* d_cost3,
-                           void* stream) {
-  if (!c) return ME_EINVAL;
-  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
-  me_status s =
-      check_args(c, d_ref0, d_cur, width, height, stride, blk, 0, search_cost(cost), d_mv_q0);
-  if (s != ME_OK) return s;
-  if ((s = check_bipred(c, cost, d_ref1, d_mv_q1, d_mv_out0, d_mv_out1, d_mode)) != ME_OK) return s;
-  // frames must not overlap and a plane stack stays below 2 GiB, as in
-  // me_refine_qpel_device
-  const unsigned long long fb = (unsigned long long)stride * height;
-  const size_t fs[3] = {ref0_frame_stride, ref1_frame_stride, cur_frame_stride};
-  for (size_t v : fs) {
-    if (n_frames > 1 && v < fb)
-      return fail(c, ME_EINVAL, "frame stride %zu below a frame's %llu bytes", v, fb);
-    const unsigned long long bytes = (unsigned long long)(n_frames - 1) * v + fb;
-    if (bytes >= (1ull << 31))
-      return fail(c, ME_EUNSUPPORTED, "batch of %llu bytes (limit 2 GiB)", bytes);
-  }
-  c->err[0] = 0;
-  return bipred_on(c, c->devs[0], d_ref0, ref0_frame_stride, d_ref1, ref1_frame_stride, d_cur,
-                   cur_frame_stride, width, height, stride, blk, cost, refine, n_frames, d_mv_q0,
-                   d_mv_q1, d_mv_out0, d_mv_out1, d_mode, d_block_cost, d_cost3,
-                   (hipStream_t)stream);
-}
-
-// Device buffers of the host bi-prediction calls on d.stream: three packed
-// planes (d.ref = ref0, d.cur, then ref1) and the records of nb blocks in
-// d.rec.
-struct BipredBufs {
-  uint8_t* ref1;
-  int16_t *q0, *q1;
-  uint32_t *cost, *cost3;
-  uint8_t* mode;
-};
-static me_status upload_triple(me_ctx* c, Dev& d, const uint8_t* ref0, const uint8_t* ref1,
-                               const uint8_t* cur, int width, int height, int stride, size_t nb,
-                               BipredBufs* B) {
-  HIPCHK(c, hipSetDevice(d.id));
-  me_status s = me::own_stream(c, d);
-  if (s != ME_OK) return s;
-  const size_t plane = (size_t)width * height;
-  if ((s = grow(c, (void**)&d.ref, &d.frame_cap, 3 * plane)) != ME_OK) return s;
-  d.cur = d.ref + plane;
-  B->ref1 = d.ref + 2 * plane;
-  // q0 | q1 | cost | cost3 | mode: 4 + 4 + 4 + 12 + 1 bytes per block
-  if ((s = grow(c, (void**)&d.rec, &d.rec_cap, nb * 28)) != ME_OK) return s;
-  B->q0 = reinterpret_cast<int16_t*>(d.rec);
-  B->q1 = reinterpret_cast<int16_t*>(d.rec + nb * 4);
-  B->cost = reinterpret_cast<uint32_t*>(d.rec + nb * 8);
-  B->cost3 = reinterpret_cast<uint32_t*>(d.rec + nb * 12);
-  B->mode = reinterpret_cast<uint8_t*>(d.rec + nb * 24);
-  HIPCHK(c, hipMemcpy2DAsync(d.ref, width, ref0, stride, width, height, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(c, hipMemcpy2DAsync(d.cur, width, cur, stride, width, height, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(c, hipMemcpy2DAsync(B->ref1, width, ref1, stride, width, height, hipMemcpyHostToDevice, d.stream));
-  return ME_OK;
-}
-
-me_status me_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* ref1, const uint8_t* cur,
-                    int width, int height, int stride, int blk, me_cost cost, int refine,
-                    const int16_t* mv_q0, const int16_t* mv_q1, int16_t* mv_out0,
-                    int16_t* mv_out1, uint8_t* mode, uint32_t* block_cost, uint32_t* cost3) {
-  me_status s =
-      check_args(c, ref0, cur, width, height, stride, blk, 0, search_cost(cost), mv_q0);
-  if (s != ME_OK) return s;
-  if ((s = check_bipred(c, cost, ref1, mv_q1, mv_out0, mv_out1, mode)) != ME_OK) return s;
-  const size_t nb = (size_t)me_num_blocks(width, height, blk);
-  for (size_t i = 0; i < 2 * nb; i++)
-    for (const int16_t* q : {mv_q0, mv_q1})
-      if (q[i] > ME_BIPRED_MAX_Q || q[i] < -ME_BIPRED_MAX_Q)
-        return fail(c, ME_EINVAL, "block %zu: vector component %d beyond ME_BIPRED_MAX_Q (%d)",
-                    i / 2, (int)q[i], ME_BIPRED_MAX_Q);
-  c->err[0] = 0;
-  Dev& d = c->devs[0];
-  BipredBufs B;
-  if ((s = upload_triple(c, d, ref0, ref1, cur, width, height, stride, nb, &B)) != ME_OK) return s;
-  HIPCHK(c, hipMemcpyAsync(B.q0, mv_q0, nb * 4, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(c, hipMemcpyAsync(B.q1, mv_q1, nb * 4, hipMemcpyHostToDevice, d.stream));
-  if ((s = bipred_on(c, d, d.ref, 0, B.ref1, 0, d.cur, 0, width, height, width, blk, cost, refine,
-                     1, B.q0, B.q1, B.q0, B.q1, B.mode, B.cost, B.cost3, d.stream)) != ME_OK)
-    return s;
-  HIPCHK(c, hipMemcpyAsync(mv_out0, B.q0, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipMemcpyAsync(mv_out1, B.q1, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipMemcpyAsync(mode, B.mode, nb, hipMemcpyDeviceToHost, d.stream));
-  if (block_cost)
-    HIPCHK(c, hipMemcpyAsync(block_cost, B.cost, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  if (cost3) HIPCHK(c, hipMemcpyAsync(cost3, B.cost3, nb * 12, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipStreamSynchronize(d.stream));
-  return ME_OK;
-}
-
-me_status me_full_search_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* ref1,
-                                const uint8_t* cur, int width, int height, int stride, int blk,
-                                int range, me_cost cost, int16_t* mv_out0, int16_t* mv_out1,
-                                uint8_t* mode, uint32_t* block_cost) {
-  me_status s =
-      check_args(c, ref0, cur, width, height, stride, blk, range, search_cost(cost), mv_out0);
-  if (s != ME_OK) return s;
-  if ((s = check_bipred(c, cost, ref1, mv_out1, mv_out0, mv_out1, mode)) != ME_OK) return s;
-  if (c->devs.size() > 1)
-    return fail(c, ME_EUNSUPPORTED, "bi-predictive search on %zu devices (one device only)",
-                c->devs.size());
-  c->err[0] = 0;
-  Dev& d = c->devs[0];
-  const size_t nb = (size_t)me_num_blocks(width, height, blk);
-  BipredBufs B;
-  if ((s = upload_triple(c, d, ref0, ref1, cur, width, height, stride, nb, &B)) != ME_OK) return s;
-  const int nby = (height + blk - 1) / blk;
-  // search and refine against ref0, then ref1 (B.cost is overwritten by each
-  // stage; the bi-prediction's is the one that is read back)
-  const uint8_t* refs[2] = {d.ref, B.ref1};
-  int16_t* fields[2] = {B.q0, B.q1};
-  for (int k = 0; k < 2; k++) {
-    const me::SearchJob J{refs[k], 0, d.cur, 0, 0, nby, fields[k], B.cost};
-    // (SATD: the integer searches run at SAD)
-    me::SearchArgs p = make_args(J, width, height, width, blk, range, search_cost(cost));
-    if ((s = attach_scratch(c, d, p)) != ME_OK) return s;
-    if ((s = launch_ordered(c, d, p, &J, 1, d.stream)) != ME_OK) return s;
-    // the searched vectors stay inside the window (|m| <= ME_MAX_RANGE): refine in place
-    if ((s = refine_on(c, d, refs[k], 0, d.cur, 0, width, height, width, blk, cost, 1, fields[k],
-                       fields[k], B.cost, d.stream)) != ME_OK)
-      return s;
-  }
-  if ((s = bipred_on(c, d, d.ref, 0, B.ref1, 0, d.cur, 0, width, height, width, blk, cost, 1, 1,
-                     B.q0, B.q1, B.q0, B.q1, B.mode, B.cost, nullptr, d.stream)) != ME_OK)
-    return s;
-  HIPCHK(c, hipMemcpyAsync(mv_out0, B.q0, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipMemcpyAsync(mv_out1, B.q1, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipMemcpyAsync(mode, B.mode, nb, hipMemcpyDeviceToHost, d.stream));
-  if (block_cost)
-    HIPCHK(c, hipMemcpyAsync(block_cost, B.cost, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  return me::device_status(c, d, d.stream);
-}
-
-static me_status compensate_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* ref1,
-                                   const uint8_t* cur, int width, int height, int blk,
-                                   const int16_t* mv0, const int16_t* mv1, const uint8_t* mode,
-                                   uint8_t* out, int planes, double* psnr) {
-  me_status s = check_args(c, ref0, cur ? cur : ref0, width, height, width, blk, 0, ME_COST_SSD, mv0);
-  if (s != ME_OK) return s;
-  if (!ref1 || !mv1 || !mode || !out)
-    return fail(c, ME_EINVAL, "null bi-prediction plane, field, mode or output pointer");
-  const size_t nb = (size_t)me_num_blocks(width, height, blk);
-  for (size_t i = 0; i < nb; i++)
-    if (mode[i] > ME_PRED_BI)
-      return fail(c, ME_EINVAL, "block %zu: mode %d (0, 1 or 2)", i, (int)mode[i]);
-  Dev& d = c->devs[0];
-  BipredBufs B;
-  if ((s = upload_triple(c, d, ref0, ref1, cur ? cur : ref0, width, height, width, nb, &B)) != ME_OK)
-    return s;
-  const size_t plane = (size_t)width * height;
-  size_t scap = d.stats ? 16 : 0;
-  if ((s = grow(c, (void**)&d.stats, &scap, 16)) != ME_OK) return s;
-  const size_t out_bytes = planes ? 5 * plane : plane;
-  if ((s = grow(c, (void**)&d.out5, &d.out_cap, out_bytes)) != ME_OK) return s;
-  HIPCHK(c, hipMemcpyAsync(B.q0, mv0, nb * 4, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(c, hipMemcpyAsync(B.q1, mv1, nb * 4, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(c, hipMemcpyAsync(B.mode, mode, nb, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(c, hipMemsetAsync(d.stats, 0, 16, d.stream));
-  HIPCHK(c, me::launch_bipred_compensate(d.ref, B.ref1, d.cur, width, height, blk, B.q0, B.q1,
-                                         B.mode, d.out5, planes, d.stats, d.stream));
-  unsigned long long st[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(out, d.out5, out_bytes, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipMemcpyAsync(st, d.stats, 16, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipStreamSynchronize(d.stream));
-  if (psnr) {  // as compensate()
-    double mse = (double)st[0];
-    mse /= (double)width * height;
-    *psnr = mse == 0 ? 99.0 : 20 * log10((double)st[1]) - 10 * log10(mse);
-  }
-  return ME_OK;
-}
-
-me_status me_motion_compensate_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* ref1,
-                                      int width, int height, int blk, const int16_t* mv0,
-                                      const int16_t* mv1, const uint8_t* mode, uint8_t* mc) {
-  return compensate_bipred(c, ref0, ref1, nullptr, width, height, blk, mv0, mv1, mode, mc, 0,
-                           nullptr);
-}
-
-me_status me_compensate_planes_bipred(me_ctx* c, const uint8_t* ref0, const uint8_t* ref1,
-                                      const uint8_t* cur, int width, int height, int blk,
-                                      const int16_t* mv0, const int16_t* mv1, const uint8_t* mode,
-                                      uint8_t* out5, double* psnr) {
-  if (!cur) return fail(c, ME_EINVAL, "null cur");
-  return compensate_bipred(c, ref0, ref1, cur, width, height, blk, mv0, mv1, mode, out5, 1, psnr);
-}
-
-// ---- partition search (me_partition.hip, me_partition_plan.cpp) ----
-
-// The search's own argument rules; *n: the four grids' cell counts.
-static me_status check_partition(me_ctx* c, const void* ref, const void* cur, int width, int height,
-                                 int stride, int blk, int range, me_cost cost, uint32_t lambda,
-                                 const me_part_fields* out, int n[4]) {
-  if (!c) return ME_EINVAL;
-  if (!ref || !cur || !out) return fail(c, ME_EINVAL, "null plane or field pointer");
-  if (!out->mv_2nx2n || !out->mv_2nxn || !out->mv_nx2n || !out->mv_nxn || !out->mode)
-    return fail(c, ME_EINVAL, "null partition vector field or mode array");
-  if (cost != ME_COST_SSD && cost != ME_COST_SAD && cost != ME_COST_SSIM && cost != ME_COST_SATD)
-    return fail(c, ME_EINVAL, "cost %d", (int)cost);
-  const char* why = "";
-  const me_status s = me::partition_check(width, height, stride, blk, range, &why);
-  if (s != ME_OK) return fail(c, s, "%s (%dx%d pitch %d, B %d, S %d)", why, width, height, stride,
-                              blk, range);
-  if (cost != ME_COST_SAD)
-    return fail(c, ME_EUNSUPPORTED, "partition search costs SAD only");
-  if (lambda > ME_PART_MAX_LAMBDA)
-    return fail(c, ME_EINVAL, "lambda %u above ME_PART_MAX_LAMBDA", lambda);
-  if (c->devs.size() > 1)
-    return fail(c, ME_EUNSUPPORTED, "partition search on %zu devices (one device only)",
-                c->devs.size());
-  if (me_partition_counts(width, height, blk, n) != ME_OK)
-    return fail(c, ME_EINVAL, "frame %dx%d", width, height);
-  return ME_OK;
-}
-
-// Enqueue the search of n_frames frames on s after the device's previous
-// search (not while capturing: me_graph_launch orders the graph).
-static me_status partition_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rfs,
-                              const uint8_t* d_cur, size_t cfs, int width, int height, int stride,
-                              int blk, int range, uint32_t lambda, int n_frames,
-                              const me_part_fields& out, hipStream_t s) {
-  if (!me::capturing(s)) {
-    me_status st = me::order_on(c, d, s);
-    if (st != ME_OK) return st;
-  }
-  // the kernel me_partition_kernel_variant names; its LDS DMA also needs
-  // planes and frame strides that are multiples of 4 bytes
-  const bool fast =
-      me_partition_kernel_variant(width, height, stride, blk, range) == ME_PART_KERNEL_FAST &&
-      ((uintptr_t)d_ref | (uintptr_t)d_cur | (n_frames > 1 ? rfs | cfs : 0)) % 4 == 0;
-  const hipError_t e = me::launch_partition_search(d_ref, rfs, d_cur, cfs, width, height, stride,
-                                                   blk, range, lambda, n_frames, fast, out, s);
-  if (e != hipSuccess)
-    return me::fail(c, ME_EDEVICE, "partition search launch: %s", hipGetErrorString(e));
-  return ME_OK;
-}
-
-me_status me_partition_search_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
-                                     const uint8_t* d_cur, size_t cur_frame_stride, int width,
-                                     int height, int stride, int blk, int range, me_cost cost,
-                                     uint32_t lambda, int n_frames, const me_part_fields* d_out,
-                                     void* stream) {
-  if (!c) return ME_EINVAL;
-  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
-  int n[4];
-  me_status s = check_partition(c, d_ref, d_cur, width, height, stride, blk, range, cost, lambda,
-                                d_out, n);
-  if (s != ME_OK) return s;
-  // frames must not overlap and a plane stack stays below 2 GiB, as in
-  // me_refine_qpel_device
-  const unsigned long long fb = (unsigned long long)stride * height;
-  if (n_frames > 1 && (ref_frame_stride < fb || cur_frame_stride < fb))
-    return fail(c, ME_EINVAL, "frame strides %zu / %zu below a frame's %llu bytes",
-                ref_frame_stride, cur_frame_stride, fb);
-  const unsigned long long rb = (unsigned long long)(n_frames - 1) * ref_frame_stride + fb;
-  const unsigned long long cb = (unsigned long long)(n_frames - 1) * cur_frame_stride + fb;
-  if (rb >= (1ull << 31) || cb >= (1ull << 31))
-    return fail(c, ME_EUNSUPPORTED, "batch of %llu / %llu bytes (limit 2 GiB)", rb, cb);
-  c->err[0] = 0;
-  Dev& d = c->devs[0];
-  return partition_on(c, d, d_ref, ref_frame_stride, d_cur, cur_frame_stride, width, height,
-                      stride, blk, range, lambda, n_frames, *d_out, (hipStream_t)stream);
-}
-
-me_status me_partition_search(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
-                              int height, int stride, int blk, int range, me_cost cost,
-                              uint32_t lambda, const me_part_fields* out) {
-  int n[4];
-  me_status s = check_partition(c, ref, cur, width, height, stride, blk, range, cost, lambda, out, n);
-  if (s != ME_OK) return s;
-  c->err[0] = 0;
-  Dev& d = c->devs[0];
-  // records in d.rec: the four vector fields, the four cost fields, the mode
-  // costs (4 bytes per cell each), then the mode bytes
-  const size_t cells = (size_t)n[0] + n[1] + n[2] + n[3];
-  const size_t bytes = 8 * cells + 4 * (size_t)n[0] + (size_t)n[0];
-  if ((s = upload_pair(c, d, ref, cur, width, height, stride, (bytes + 7) / 8)) != ME_OK) return s;
-  me_part_fields D;
-  uint8_t* p = d.rec;
-  int16_t** mv[4] = {&D.mv_2nx2n, &D.mv_2nxn, &D.mv_nx2n, &D.mv_nxn};
-  uint32_t** co[4] = {&D.cost_2nx2n, &D.cost_2nxn, &D.cost_nx2n, &D.cost_nxn};
-  for (int g = 0; g < 4; g++) *mv[g] = reinterpret_cast<int16_t*>(p), p += 4 * (size_t)n[g];
-  for (int g = 0; g < 4; g++) *co[g] = reinterpret_cast<uint32_t*>(p), p += 4 * (size_t)n[g];
-  D.mode_cost = reinterpret_cast<uint32_t*>(p), p += 4 * (size_t)n[0];
-  D.mode = p;
-  if ((s = partition_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, range, lambda, 1, D,
-                        d.stream)) != ME_OK)
-    return s;
-  int16_t* const hmv[4] = {out->mv_2nx2n, out->mv_2nxn, out->mv_nx2n, out->mv_nxn};
-  uint32_t* const hco[4] = {out->cost_2nx2n, out->cost_2nxn, out->cost_nx2n, out->cost_nxn};
-  for (int g = 0; g < 4; g++) {
-    HIPCHK(c, hipMemcpyAsync(hmv[g], *mv[g], 4 * (size_t)n[g], hipMemcpyDeviceToHost, d.stream));
-    if (hco[g])
-      HIPCHK(c, hipMemcpyAsync(hco[g], *co[g], 4 * (size_t)n[g], hipMemcpyDeviceToHost, d.stream));
-  }
-  HIPCHK(c, hipMemcpyAsync(out->mode, D.mode, (size_t)n[0], hipMemcpyDeviceToHost, d.stream));
-  if (out->mode_cost)
-    HIPCHK(c, hipMemcpyAsync(out->mode_cost, D.mode_cost, 4 * (size_t)n[0], hipMemcpyDeviceToHost,
-                             d.stream));
-  HIPCHK(c, hipStreamSynchronize(d.stream));
-  return ME_OK;
-}
-
-me_status me_partition_leaf_field_device(me_ctx* c, int width, int height, int blk, int n_frames,
-                                         const me_part_fields* d_in, int16_t* d_leaf_mv,
-                                         void* stream) {
-  if (!c) return ME_EINVAL;
-  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
-  if (!d_in || !d_leaf_mv || !d_in->mv_2nx2n || !d_in->mv_2nxn || !d_in->mv_nx2n ||
-      !d_in->mv_nxn || !d_in->mode)
-    return fail(c, ME_EINVAL, "null partition vector field, mode array or leaf field");
-  const char* why = "";
-  const me_status s = me::partition_check(width, height, width, blk, 0, &why);
-  if (s != ME_OK) return fail(c, s, "%s (%dx%d, B %d)", why, width, height, blk);
-  if (c->devs.size() > 1)
-    return fail(c, ME_EUNSUPPORTED, "partition leaf field on %zu devices (one device only)",
-                c->devs.size());
-  c->err[0] = 0;
-  Dev& d = c->devs[0];
-  hipStream_t st = (hipStream_t)stream;
-  if (!me::capturing(st)) {
-    const me_status o = me::order_on(c, d, st);
-    if (o != ME_OK) return o;
-  }
-  const hipError_t e = me::launch_partition_leaf(width, height, blk, n_frames, *d_in, d_leaf_mv, st);
-  if (e != hipSuccess)
-    return me::fail(c, ME_EDEVICE, "partition leaf field launch: %s", hipGetErrorString(e));
-  return ME_OK;
-}
-
-// ---- rate-constrained search (me_rd.hip, me_rd_plan.cpp, me_subpel.hip) ----
-
-// The argument rules shared by the search and the refinement entry points.
-static me_status check_rd_ctx(me_ctx* c, uint32_t lambda, const char* what) {
-  if (lambda > ME_RD_MAX_LAMBDA)
-    return fail(c, ME_EINVAL, "lambda %u above ME_RD_MAX_LAMBDA", lambda);
-  if (c->devs.size() > 1)
-    return fail(c, ME_EUNSUPPORTED, "%s on %zu devices (one device only)", what, c->devs.size());
-  return ME_OK;
-}
-
-// The search's own argument rules.
-static me_status check_rd(me_ctx* c, const void* ref, const void* cur, int width, int height,
-                          int stride, int blk, int range, me_cost cost, uint32_t lambda,
-                          const void* mv, const void* block_cost) {
-  if (!c) return ME_EINVAL;
-  if (!ref || !cur || !mv || !block_cost)
-    return fail(c, ME_EINVAL, "null plane, vector or cost pointer");
-  if (cost != ME_COST_SSD && cost != ME_COST_SAD && cost != ME_COST_SSIM && cost != ME_COST_SATD)
-    return fail(c, ME_EINVAL, "cost %d", (int)cost);
-  const char* why = "";
-  const me_status s = me::rd_check(width, height, stride, blk, range, lambda, &why);
-  if (s != ME_OK)
-    return fail(c, s, "%s (%dx%d pitch %d, B %d, S %d, lambda %u)", why, width, height, stride,
-                blk, range, lambda);
-  if (cost != ME_COST_SAD)
-    return fail(c, ME_EUNSUPPORTED, "rate-constrained search costs SAD only");
-  return check_rd_ctx(c, lambda, "rate-constrained search");
-}
-
-// Frames must not overlap and a plane stack stays below 2 GiB, as in
-// me_refine_qpel_device.
-static me_status check_frame_strides(me_ctx* c, int stride, int height, int n_frames, size_t rfs,
-                                     size_t cfs) {
-  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
-  const unsigned long long fb = (unsigned long long)stride * height;
-  if (n_frames > 1 && (rfs < fb || cfs < fb))
-    return fail(c, ME_EINVAL, "frame strides %zu / %zu below a frame's %llu bytes", rfs, cfs, fb);
-  const unsigned long long rb = (unsigned long long)(n_frames - 1) * rfs + fb;
-  const unsigned long long cb = (unsigned long long)(n_frames - 1) * cfs + fb;
-  if (rb >= (1ull << 31) || cb >= (1ull << 31))
-    return fail(c, ME_EUNSUPPORTED, "batch of %llu / %llu bytes (limit 2 GiB)", rb, cb);
-  return ME_OK;
-}
-
-// Enqueue the search of n_frames frames on s after the device's previous
-// search (not while capturing: me_graph_launch orders the graph).
-static me_status rd_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rfs, const uint8_t* d_cur,
-                       size_t cfs, int width, int height, int stride, int blk, int range,
-                       uint32_t lambda, int n_frames, const int16_t* d_pred, int16_t* d_mv,
-                       uint32_t* d_cost, uint32_t* d_dist, uint8_t* d_bits, hipStream_t s) {
-  if (!me::capturing(s)) {
-    me_status st = me::order_on(c, d, s);
-    if (st != ME_OK) return st;
-  }
-  // the kernel me_rd_kernel_variant names; its LDS DMA also needs planes and
-  // frame strides that are multiples of 4 bytes
-  const bool fast =
-      me_rd_kernel_variant(width, height, stride, blk, range, lambda) == ME_RD_KERNEL_FAST &&
-      ((uintptr_t)d_ref | (uintptr_t)d_cur | (n_frames > 1 ? rfs | cfs : 0)) % 4 == 0;
-  const hipError_t e = me::launch_rd_search(d_ref, rfs, d_cur, cfs, width, height, stride, blk,
-                                            range, lambda, n_frames, fast, d_pred, d_mv, d_cost,
-                                            d_dist, d_bits, s);
-  if (e != hipSuccess)
-    return me::fail(c, ME_EDEVICE, "rate-constrained search launch: %s", hipGetErrorString(e));
-  return ME_OK;
-}
-
-static me_status refine_rd_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rfs,
-                              const uint8_t* d_cur, size_t cfs, int width, int height, int stride,
-                              int blk, me_cost cost, uint32_t lambda, int n_frames,
-                              const int16_t* d_pred, const int16_t* d_mv, int16_t* d_q,
-                              uint32_t* d_cost, uint32_t* d_dist, hipStream_t s) {
-  if (!me::capturing(s)) {
-    me_status st = me::order_on(c, d, s);
-    if (st != ME_OK) return st;
-  }
-  const hipError_t e = me::launch_qpel_refine_rd(d_ref, rfs, d_cur, cfs, width, height, stride,
-                                                 blk, cost, lambda, n_frames,
-                                                 d_pred, d_mv, d_q, d_cost, d_dist, s);
-  if (e != hipSuccess)
-    return me::fail(c, ME_EDEVICE, "rate-constrained refinement launch: %s",
-                    hipGetErrorString(e));
-  return ME_OK;
-}
-
-me_status me_rd_search_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
-                              const uint8_t* d_cur, size_t cur_frame_stride, int width,
-                              int height, int stride, int blk, int range, me_cost cost,
-                              uint32_t lambda, int n_frames, const int16_t* d_pred_q,
-                              int16_t* d_mv_xy, uint32_t* d_block_cost, uint32_t* d_block_dist,
-                              uint8_t* d_block_bits, void* stream) {
-  me_status s = check_rd(c, d_ref, d_cur, width, height, stride, blk, range, cost, lambda,
-                         d_mv_xy, d_block_cost);
-  if (s != ME_OK) return s;
-  if ((s = check_frame_strides(c, stride, height, n_frames, ref_frame_stride,
-                               cur_frame_stride)) != ME_OK)
-    return s;
-  c->err[0] = 0;
-  return rd_on(c, c->devs[0], d_ref, ref_frame_stride, d_cur, cur_frame_stride, width, height,
-               stride, blk, range, lambda, n_frames, d_pred_q, d_mv_xy, d_block_cost,
-               d_block_dist, d_block_bits, (hipStream_t)stream);
-}
-
-// d.rec as [pred | mv | cost | dist] of nb blocks (4 bytes each per block),
-// then one byte per block; pred uploaded (zeros for a null predictor).
-struct RdRec {
-  int16_t *pred, *mv;
-  uint32_t *cost, *dist;
-  uint8_t* bits;
-};
-static me_status rd_records(me_ctx* c, Dev& d, size_t nb, const int16_t* pred_q, RdRec* r) {
-  r->pred = reinterpret_cast<int16_t*>(d.rec);
-  r->mv = reinterpret_cast<int16_t*>(d.rec + 4 * nb);
-  r->cost = reinterpret_cast<uint32_t*>(d.rec + 8 * nb);
-  r->dist = reinterpret_cast<uint32_t*>(d.rec + 12 * nb);
-  r->bits = d.rec + 16 * nb;
-  if (pred_q)
-    HIPCHK(c, hipMemcpyAsync(r->pred, pred_q, nb * 4, hipMemcpyHostToDevice, d.stream));
-  else
-    r->pred = nullptr;
-  return ME_OK;
-}
-
-me_status me_rd_search(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width, int height,
-                       int stride, int blk, int range, me_cost cost, uint32_t lambda,
-                       const int16_t* pred_q, int16_t* mv_xy, uint32_t* block_cost,
-                       uint32_t* block_dist, uint8_t* block_bits) {
-  me_status s = check_rd(c, ref, cur, width, height, stride, blk, range, cost, lambda, mv_xy,
-                         block_cost);
-  if (s != ME_OK) return s;
-  c->err[0] = 0;
-  Dev& d = c->devs[0];
-  const size_t nb = (size_t)me_num_blocks(width, height, blk);
-  if ((s = upload_pair(c, d, ref, cur, width, height, stride, (17 * nb + 7) / 8)) != ME_OK)
-    return s;
-  RdRec r;
-  if ((s = rd_records(c, d, nb, pred_q, &r)) != ME_OK) return s;
-  if ((s = rd_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, range, lambda, 1, r.pred,
-                 r.mv, r.cost, r.dist, r.bits, d.stream)) != ME_OK)
-    return s;
-  HIPCHK(c, hipMemcpyAsync(mv_xy, r.mv, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipMemcpyAsync(block_cost, r.cost, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  if (block_dist)
-    HIPCHK(c, hipMemcpyAsync(block_dist, r.dist, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  if (block_bits)
-    HIPCHK(c, hipMemcpyAsync(block_bits, r.bits, nb, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipStreamSynchronize(d.stream));
-  return ME_OK;
-}
-
-me_status me_refine_qpel_rd_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
-                                   const uint8_t* d_cur, size_t cur_frame_stride, int width,
-                                   int height, int stride, int blk, me_cost cost, uint32_t lambda,
-                                   int n_frames, const int16_t* d_pred_q, const int16_t* d_mv_xy,
-                                   int16_t* d_mv_q, uint32_t* d_block_cost,
-                                   uint32_t* d_block_dist, void* stream) {
-  if (!c) return ME_EINVAL;
-  me_status s =
-      check_args(c, d_ref, d_cur, width, height, stride, blk, 0, search_cost(cost), d_mv_xy);
-  if (s != ME_OK) return s;
-  if ((s = check_qpel(c, cost, d_mv_q)) != ME_OK) return s;
-  if ((s = check_rd_ctx(c, lambda, "rate-constrained refinement")) != ME_OK) return s;
-  if ((s = check_frame_strides(c, stride, height, n_frames, ref_frame_stride,
-                               cur_frame_stride)) != ME_OK)
-    return s;
-  c->err[0] = 0;
-  return refine_rd_on(c, c->devs[0], d_ref, ref_frame_stride, d_cur, cur_frame_stride, width,
-                      height, stride, blk, cost, lambda, n_frames, d_pred_q, d_mv_xy, d_mv_q,
-                      d_block_cost, d_block_dist, (hipStream_t)stream);
-}
-
-me_status me_refine_qpel_rd(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
-                            int height, int stride, int blk, me_cost cost, uint32_t lambda,
-                            const int16_t* pred_q, const int16_t* mv_xy, int16_t* mv_q,
-                            uint32_t* block_cost, uint32_t* block_dist) {
-  me_status s = check_args(c, ref, cur, width, height, stride, blk, 0, search_cost(cost), mv_xy);
-  if (s != ME_OK) return s;
-  if ((s = check_qpel(c, cost, mv_q)) != ME_OK) return s;
-  if ((s = check_rd_ctx(c, lambda, "rate-constrained refinement")) != ME_OK) return s;
-  const size_t nb = (size_t)me_num_blocks(width, height, blk);
-  for (size_t i = 0; i < 2 * nb; i++)
-    if (mv_xy[i] > ME_QPEL_MAX_MV || mv_xy[i] < -ME_QPEL_MAX_MV)
-      return fail(c, ME_EINVAL, "block %zu: vector component %d beyond ME_QPEL_MAX_MV (%d)", i / 2,
-                  (int)mv_xy[i], ME_QPEL_MAX_MV);
-  c->err[0] = 0;
-  Dev& d = c->devs[0];
-  if ((s = upload_pair(c, d, ref, cur, width, height, stride, (17 * nb + 7) / 8)) != ME_OK)
-    return s;
-  RdRec r;
-  if ((s = rd_records(c, d, nb, pred_q, &r)) != ME_OK) return s;
-  HIPCHK(c, hipMemcpyAsync(r.mv, mv_xy, nb * 4, hipMemcpyHostToDevice, d.stream));
-  if ((s = refine_rd_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, cost, lambda, 1,
-                        r.pred, r.mv, r.mv, r.cost, r.dist, d.stream)) != ME_OK)
-    return s;
-  HIPCHK(c, hipMemcpyAsync(mv_q, r.mv, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  if (block_cost)
-    HIPCHK(c, hipMemcpyAsync(block_cost, r.cost, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  if (block_dist)
-    HIPCHK(c, hipMemcpyAsync(block_dist, r.dist, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipStreamSynchronize(d.stream));
-  return ME_OK;
-}
-
-me_status me_full_search_rd_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
-                                 int height, int stride, int blk, int range, me_cost cost,
-                                 uint32_t lambda, const int16_t* pred_q, int16_t* mv_q,
-                                 uint32_t* block_cost) {
-  // (block_cost is optional here: the search's own cost array is d.rec's)
-  // (SATD: the search runs at SAD, the refinement at SATD)
-  me_status s = check_rd(c, ref, cur, width, height, stride, blk, range, search_cost(cost), lambda,
-                         mv_q, mv_q);
-  if (s != ME_OK) return s;
-  c->err[0] = 0;
-  Dev& d = c->devs[0];
-  const size_t nb = (size_t)me_num_blocks(width, height, blk);
-  if ((s = upload_pair(c, d, ref, cur, width, height, stride, (17 * nb + 7) / 8)) != ME_OK)
-    return s;
-  RdRec r;
-  if ((s = rd_records(c, d, nb, pred_q, &r)) != ME_OK) return s;
-  if ((s = rd_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, range, lambda, 1, r.pred,
-                 r.mv, r.cost, nullptr, nullptr, d.stream)) != ME_OK)
-    return s;
-  // the searched vectors stay inside the window (|m| <= ME_RD_MAX_RANGE): refine in place
-  if ((s = refine_rd_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, cost, lambda, 1,
-                        r.pred, r.mv, r.mv, r.cost, nullptr, d.stream)) != ME_OK)
-    return s;
-  HIPCHK(c, hipMemcpyAsync(mv_q, r.mv, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  if (block_cost)
-    HIPCHK(c, hipMemcpyAsync(block_cost, r.cost, nb * 4, hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipStreamSynchronize(d.stream));
-  return ME_OK;
-}
-
-// ---- rate-constrained partition search (me_partition_rd.hip) ----
-
-// me_partition_search's argument rules with this search's lambda limit.
-static me_status check_partition_rd(me_ctx* c, const void* ref, const void* cur, int width,
-                                    int height, int stride, int blk, int range, me_cost cost,
-                                    uint32_t lambda, const me_part_rd_fields* out, int n[4]) {
-  if (!c) return ME_EINVAL;
-  if (!out) return fail(c, ME_EINVAL, "null plane or field pointer");
-  const me_status s = check_partition(c, ref, cur, width, height, stride, blk, range, cost, 0,
-                                      &out->f, n);
-  if (s != ME_OK) return s;
-  if (lambda > ME_PART_RD_MAX_LAMBDA)
-    return fail(c, ME_EINVAL, "lambda %u above ME_PART_RD_MAX_LAMBDA", lambda);
-  return ME_OK;
-}
-
-// Enqueue the search of n_frames frames on s after the device's previous
-// search (not while capturing: me_graph_launch orders the graph).
-static me_status partition_rd_on(me_ctx* c, Dev& d, const uint8_t* d_ref, size_t rfs,
-                                 const uint8_t* d_cur, size_t cfs, int width, int height,
-                                 int stride, int blk, int range, uint32_t lambda, int n_frames,
-                                 const int16_t* d_pred, const me_part_rd_fields& out,
-                                 hipStream_t s) {
-  if (!me::capturing(s)) {
-    me_status st = me::order_on(c, d, s);
-    if (st != ME_OK) return st;
-  }
-  // the kernel me_partition_rd_kernel_variant names; its LDS DMA also needs
-  // planes and frame strides that are multiples of 4 bytes
-  const bool fast = me_partition_rd_kernel_variant(width, height, stride, blk, range, lambda) ==
-                        ME_PART_KERNEL_FAST &&
-                    ((uintptr_t)d_ref | (uintptr_t)d_cur | (n_frames > 1 ? rfs | cfs : 0)) % 4 == 0;
-  const hipError_t e = me::launch_partition_rd_search(d_ref, rfs, d_cur, cfs, width, height,
-                                                      stride, blk, range, lambda, n_frames, fast,
-                                                      d_pred, out, s);
-  if (e != hipSuccess)
-    return me::fail(c, ME_EDEVICE, "rate-constrained partition search launch: %s",
-                    hipGetErrorString(e));
-  return ME_OK;
-}
-
-me_status me_partition_rd_search_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
-                                        const uint8_t* d_cur, size_t cur_frame_stride, int width,
-                                        int height, int stride, int blk, int range, me_cost cost,
-                                        uint32_t lambda, int n_frames, const int16_t* d_pred_q,
-                                        const me_part_rd_fields* d_out, void* stream) {
-  if (!c) return ME_EINVAL;
-  if (n_frames < 1 || n_frames > 4096) return fail(c, ME_EINVAL, "n_frames %d", n_frames);
-  int n[4];
-  me_status s = check_partition_rd(c, d_ref, d_cur, width, height, stride, blk, range, cost,
-                                   lambda, d_out, n);
-  if (s != ME_OK) return s;
-  if ((s = check_frame_strides(c, stride, height, n_frames, ref_frame_stride,
-                               cur_frame_stride)) != ME_OK)
-    return s;
-  c->err[0] = 0;
-  return partition_rd_on(c, c->devs[0], d_ref, ref_frame_stride, d_cur, cur_frame_stride, width,
-                         height, stride, blk, range, lambda, n_frames, d_pred_q, *d_out,
-                         (hipStream_t)stream);
-}
-
-me_status me_partition_rd_search(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
-                                 int height, int stride, int blk, int range, me_cost cost,
-                                 uint32_t lambda, const int16_t* pred_q,
-                                 const me_part_rd_fields* out) {
-  int n[4];
-  me_status s = check_partition_rd(c, ref, cur, width, height, stride, blk, range, cost, lambda,
-                                   out, n);
-  if (s != ME_OK) return s;
-  c->err[0] = 0;
-  Dev& d = c->devs[0];
-  // records in d.rec: the predictors, the four vector, cost and distortion
-  // fields and the mode costs (4 bytes per cell each), then the four rate
-  // fields and the mode bytes
-  const size_t cells = (size_t)n[0] + n[1] + n[2] + n[3];
-  const size_t bytes = 4 * (size_t)n[0] + 12 * cells + 4 * (size_t)n[0] + cells + (size_t)n[0];
-  if ((s = upload_pair(c, d, ref, cur, width, height, stride, (bytes + 7) / 8)) != ME_OK) return s;
-  me_part_rd_fields D;
-  uint8_t* p = d.rec;
-  int16_t* d_pred = nullptr;
-  if (pred_q) {
-    d_pred = reinterpret_cast<int16_t*>(p);
-    HIPCHK(c, hipMemcpyAsync(d_pred, pred_q, 4 * (size_t)n[0], hipMemcpyHostToDevice, d.stream));
-  }
-  p += 4 * (size_t)n[0];
-  int16_t** mv[4] = {&D.f.mv_2nx2n, &D.f.mv_2nxn, &D.f.mv_nx2n, &D.f.mv_nxn};
-  uint32_t** co[4] = {&D.f.cost_2nx2n, &D.f.cost_2nxn, &D.f.cost_nx2n, &D.f.cost_nxn};
-  uint32_t** di[4] = {&D.dist_2nx2n, &D.dist_2nxn, &D.dist_nx2n, &D.dist_nxn};
-  uint8_t** bi[4] = {&D.bits_2nx2n, &D.bits_2nxn, &D.bits_nx2n, &D.bits_nxn};
-  for (int g = 0; g < 4; g++) *mv[g] = reinterpret_cast<int16_t*>(p), p += 4 * (size_t)n[g];
-  for (int g = 0; g < 4; g++) *co[g] = reinterpret_cast<uint32_t*>(p), p += 4 * (size_t)n[g];
-  for (int g = 0; g < 4; g++) *di[g] = reinterpret_cast<uint32_t*>(p), p += 4 * (size_t)n[g];
-  D.f.mode_cost = reinterpret_cast<uint32_t*>(p), p += 4 * (size_t)n[0];
-  for (int g = 0; g < 4; g++) *bi[g] = p, p += (size_t)n[g];
-  D.f.mode = p;
-  if ((s = partition_rd_on(c, d, d.ref, 0, d.cur, 0, width, height, width, blk, range, lambda, 1,
-                           d_pred, D, d.stream)) != ME_OK)
-    return s;
-  int16_t* const hmv[4] = {out->f.mv_2nx2n, out->f.mv_2nxn, out->f.mv_nx2n, out->f.mv_nxn};
-  uint32_t* const hco[4] = {out->f.cost_2nx2n, out->f.cost_2nxn, out->f.cost_nx2n,
-                            out->f.cost_nxn};
-  uint32_t* const hdi[4] = {out->dist_2nx2n, out->dist_2nxn, out->dist_nx2n, out->dist_nxn};
-  uint8_t* const hbi[4] = {out->bits_2nx2n, out->bits_2nxn, out->bits_nx2n, out->bits_nxn};
-  for (int g = 0; g < 4; g++) {
-    const size_t b4 = 4 * (size_t)n[g];
-    HIPCHK(c, hipMemcpyAsync(hmv[g], *mv[g], b4, hipMemcpyDeviceToHost, d.stream));
-    if (hco[g]) HIPCHK(c, hipMemcpyAsync(hco[g], *co[g], b4, hipMemcpyDeviceToHost, d.stream));
-    if (hdi[g]) HIPCHK(c, hipMemcpyAsync(hdi[g], *di[g], b4, hipMemcpyDeviceToHost, d.stream));
-    if (hbi[g])
-      HIPCHK(c, hipMemcpyAsync(hbi[g], *bi[g], (size_t)n[g], hipMemcpyDeviceToHost, d.stream));
-  }
-  HIPCHK(c, hipMemcpyAsync(out->f.mode, D.f.mode, (size_t)n[0], hipMemcpyDeviceToHost, d.stream));
-  if (out->f.mode_cost)
-    HIPCHK(c, hipMemcpyAsync(out->f.mode_cost, D.f.mode_cost, 4 * (size_t)n[0],
-                             hipMemcpyDeviceToHost, d.stream));
-  HIPCHK(c, hipStreamSynchronize(d.stream));
   return ME_OK;
 }
 

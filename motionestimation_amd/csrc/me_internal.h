@@ -1,6 +1,8 @@
 // me_internal.h -- context internals shared by the C-ABI translation units
-// (me_api.hip: single-frame and stripe entry points, make_args, check_stripe,
-// attach_scratch and launch_ordered; me_stream.hip: frame-pair streaming).
+// (me_api.hip: the context, the integer searches, make_args, attach_scratch,
+// launch_ordered and upload_planes; me_api_stages.hip: the entry points that
+// work on a searched field; me_stream.hip: frame-pair streaming).  The
+// argument rules and record layouts they apply are me_api_rules.h's.
 // Not installed; include/me.h is the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,11 +13,13 @@
 #include <atomic>
 #include <condition_variable>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <thread>
 #include <vector>
 
 #include "me.h"
+#include "me_api_rules.h"
 #include "me_kernels.h"
 #include "me_tuning.h"
 
@@ -133,17 +137,19 @@ me_status fail(me_ctx* c, me_status s, const char* fmt, ...);
 // Create d's own stream if it does not exist yet (device d must be current).
 me_status own_stream(me_ctx* c, Dev& d);
 me_status grow(me_ctx* c, void** p, size_t* cap, size_t need);
-me_status check_args(me_ctx* c, const void* ref, const void* cur, int width, int height,
-                     int stride, int blk, int range, int cost, const void* mv);
+// A host entry point's n planes packed (pitch = width) back to back from d.ref
+// (d.cur: the second) on d's own stream, and d.rec grown to a layout's total.
+me_status upload_planes(me_ctx* c, Dev& d, std::initializer_list<const uint8_t*> planes, int width,
+                        int height, int stride, size_t rec_bytes);
+// Region k of d.rec under layout L.
+template <typename T>
+T* rec_at(Dev& d, const rules::Layout& L, int k) {
+  return reinterpret_cast<T*>(d.rec + L.off[k]);
+}
 // The arguments of job J's search of a frame (job_args over the geometry; no
 // context buffers yet: attach_scratch).  The base of a job list is job 0's.
 SearchArgs make_args(const SearchJob& J, int width, int height, int stride, int blk, int range,
                      int cost);
-// A stripe's block rows [r0, r1) of nby and its planes' first rows against the
-// stripe contract (include/me.h): ME_EINVAL and the message, prefixed with
-// "job <job>: " for job >= 0 (a job list), or ME_OK.
-me_status check_stripe(me_ctx* c, int nby, int blk, int range, int r0, int r1, int ref_row0,
-                       int cur_row0, int job);
 
 // Point p at d's search scratch, growing it to what p's search needs.  A
 // device's scratch serves one search at a time: launch searches that use it
@@ -209,6 +215,16 @@ struct me_ctx {
 };
 
 namespace me {
+// rules::args and rules::stripe with the context's message buffer.
+inline me_status check_args(me_ctx* c, const void* ref, const void* cur, int width, int height,
+                            int stride, int blk, int range, int cost, const void* mv) {
+  if (!c) return ME_EINVAL;
+  return rules::args(ref, cur, width, height, stride, blk, range, cost, mv, c->err, sizeof c->err);
+}
+inline me_status check_stripe(me_ctx* c, int nby, int blk, int range, int r0, int r1, int ref_row0,
+                              int cur_row0, int job) {
+  return rules::stripe(nby, blk, range, r0, r1, ref_row0, cur_row0, job, c->err, sizeof c->err);
+}
 // The last-path slot of device d of the context c serves (nullptr if d is not
 // one of its devices).
 inline std::atomic<int>* ctx_last_slot(me_ctx* c, Dev& d) {

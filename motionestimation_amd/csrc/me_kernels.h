@@ -111,14 +111,23 @@ hipError_t launch_compensate(const uint8_t* ref, const uint8_t* cur, int width, 
                              int blk, const int16_t* mv, uint8_t* out5, int write_planes,
                              unsigned long long* stats, hipStream_t stream);
 
+// The frames the batched launchers below work on: n_frames whole frames of
+// one shape, frame f's planes at ref + f * ref_frame_stride and cur + f *
+// cur_frame_stride (one frame: the strides are not read).  The searches'
+// `fast`: full-size blocks on the packed-u16 kernel (their *_kernel_variant said
+// FAST and planes and frame strides are 4-byte aligned), the clipped ones on
+// the generic kernel; otherwise every block on the generic kernel.
+struct FrameBatch {
+  const uint8_t* ref;
+  size_t ref_frame_stride;
+  const uint8_t* cur;
+  size_t cur_frame_stride;
+  int width, height, stride, blk, n_frames;
+};
+
 // Partition search (me_partition.hip; geometry in me_partition.h).
-// n_frames whole frames; out: device pointers (host struct).  fast: the
-// full-size macroblocks on the packed-u16 kernel (me_partition_kernel_variant
-// said FAST and the planes are 4-byte aligned), the clipped ones on the generic
-// kernel; otherwise every macroblock on the generic kernel.
-hipError_t launch_partition_search(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
-                                   size_t cur_frame_stride, int width, int height, int stride,
-                                   int blk, int range, uint32_t lambda, int n_frames, bool fast,
+// out: device pointers (host struct).
+hipError_t launch_partition_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,
                                    const me_part_fields& out, hipStream_t stream);
 hipError_t launch_partition_leaf(int width, int height, int blk, int n_frames,
                                  const me_part_fields& in, int16_t* leaf, hipStream_t stream);
@@ -127,37 +136,26 @@ hipError_t launch_partition_leaf(int width, int height, int blk, int n_frames,
 // launch_qpel_refine: n_frames whole frames (planes at + f * frame stride,
 // records at + 2 * f * nblk / + f * nblk); mv_out may be mv_in, cost_out may
 // be null; any int16 vector reads inside the planes.  No context scratch.
-hipError_t launch_qpel_refine(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
-                              size_t cur_frame_stride, int width, int height, int stride, int blk,
-                              int cost, int n_frames, const int16_t* mv_in, int16_t* mv_out,
+hipError_t launch_qpel_refine(const FrameBatch& b, int cost, const int16_t* mv_in, int16_t* mv_out,
                               uint32_t* cost_out, hipStream_t stream);
 // launch_qpel_refine on cost + lambda * bits(q - pred) (include/me.h
 // "rate-constrained motion search"): pred laid out like mv_in, null = all zero;
 // cost_out (J) and dist_out (the cost at the result) may be null.
-hipError_t launch_qpel_refine_rd(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
-                                 size_t cur_frame_stride, int width, int height, int stride,
-                                 int blk, int cost, uint32_t lambda, int n_frames,
-                                 const int16_t* pred, const int16_t* mv_in, int16_t* mv_out,
-                                 uint32_t* cost_out, uint32_t* dist_out, hipStream_t stream);
-// Rate-constrained integer search (me_rd.hip; geometry in me_rd.h).  n_frames
-// whole frames, records and predictors (null: all zero) at + f * nblk (x 2 for
-// vectors); dist and bits may be null.  fast: the full-size blocks on the
-// packed-u16 kernel (me_rd_kernel_variant said FAST and the planes are 4-byte
-// aligned), the clipped ones on the generic kernel; otherwise every block on
-// the generic kernel.
-hipError_t launch_rd_search(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
-                            size_t cur_frame_stride, int width, int height, int stride, int blk,
-                            int range, uint32_t lambda, int n_frames, bool fast,
+hipError_t launch_qpel_refine_rd(const FrameBatch& b, int cost, uint32_t lambda, const int16_t* pred,
+                                 const int16_t* mv_in, int16_t* mv_out, uint32_t* cost_out,
+                                 uint32_t* dist_out, hipStream_t stream);
+// Rate-constrained integer search (me_rd.hip; geometry in me_rd.h).  Records
+// and predictors (null: all zero) at + f * nblk (x 2 for vectors); dist and
+// bits may be null.
+hipError_t launch_rd_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,
                             const int16_t* pred, int16_t* mv, uint32_t* cost, uint32_t* dist,
                             uint8_t* bits, hipStream_t stream);
 // Rate-constrained partition search (me_partition_rd.hip): launch_partition_search
 // on J_p = SAD_p + lambda * bits(4 d - pred), pred [n_frames][nby][nbx][2]
-// quarter-pel or null (all zero); fast: me_partition_rd_kernel_variant's answer.
-hipError_t launch_partition_rd_search(const uint8_t* ref, size_t ref_frame_stride,
-                                      const uint8_t* cur, size_t cur_frame_stride, int width,
-                                      int height, int stride, int blk, int range, uint32_t lambda,
-                                      int n_frames, bool fast, const int16_t* pred,
-                                      const me_part_rd_fields& out, hipStream_t stream);
+// quarter-pel or null (all zero).
+hipError_t launch_partition_rd_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,
+                                      const int16_t* pred, const me_part_rd_fields& out,
+                                      hipStream_t stream);
 // launch_compensate with quarter-pel vectors and edge-replicated samples.
 hipError_t launch_qpel_compensate(const uint8_t* ref, const uint8_t* cur, int width, int height,
                                   int blk, const int16_t* mvq, uint8_t* out5, int write_planes,
@@ -168,12 +166,10 @@ hipError_t launch_qpel_compensate(const uint8_t* ref, const uint8_t* cur, int wi
 // (refine != 0) and the mode.  Frames and records laid out as for
 // launch_qpel_refine; mode_out one byte per block, cost3_out [3] per block;
 // the outputs may be the inputs, cost_out / cost3_out may be null.  No context
-// scratch; any int16 vector reads inside the planes.
-hipError_t launch_bipred(const uint8_t* ref0, size_t ref0_frame_stride, const uint8_t* ref1,
-                         size_t ref1_frame_stride, const uint8_t* cur, size_t cur_frame_stride,
-                         int width, int height, int stride, int blk, int cost, int refine,
-                         int n_frames, const int16_t* q0_in, const int16_t* q1_in, int16_t* q0_out,
-                         int16_t* q1_out, uint8_t* mode_out, uint32_t* cost_out,
+// scratch; any int16 vector reads inside the planes.  b.ref is ref0.
+hipError_t launch_bipred(const FrameBatch& b, const uint8_t* ref1, size_t ref1_frame_stride,
+                         int cost, int refine, const int16_t* q0_in, const int16_t* q1_in,
+                         int16_t* q0_out, int16_t* q1_out, uint8_t* mode_out, uint32_t* cost_out,
                          uint32_t* cost3_out, hipStream_t stream);
 // launch_qpel_compensate with two references and a mode byte (0, 1, 2) per block.
 hipError_t launch_bipred_compensate(const uint8_t* ref0, const uint8_t* ref1, const uint8_t* cur,

@@ -357,19 +357,17 @@ PartOut part_out(const me_part_fields& f, int width, int height, int blk, uint32
 
 }  // namespace
 
-hipError_t launch_partition_search(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
-                                   size_t cur_frame_stride, int width, int height, int stride,
-                                   int blk, int range, uint32_t lambda, int n_frames, bool fast,
+hipError_t launch_partition_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,
                                    const me_part_fields& out, hipStream_t stream) {
-  const PartOut o = part_out(out, width, height, blk, lambda);
-  const int nbx_full = width / blk, nby_full = height / blk;
+  const PartOut o = part_out(out, b.width, b.height, b.blk, lambda);
+  const int nbx_full = b.width / b.blk, nby_full = b.height / b.blk;
   if (fast) {
     const int rows = partition_fast_rows(range), pitch = partition_fast_pitch(range);
     const size_t lds = (size_t)((rows * pitch + 15) & ~15) + PART_TB * 256 + PART_TB * P_N * 8;
     const dim3 grid((unsigned)((nbx_full + PART_TB - 1) / PART_TB), (unsigned)nby_full,
-                    (unsigned)n_frames);
-    hipLaunchKernelGGL(me_part_fast_kernel<PART_K>, grid, dim3(PART_FAST_THREADS), lds, stream, ref,
-                       ref_frame_stride, cur, cur_frame_stride, width, height, stride, range,
+                    (unsigned)b.n_frames);
+    hipLaunchKernelGGL(me_part_fast_kernel<PART_K>, grid, dim3(PART_FAST_THREADS), lds, stream, b.ref,
+                       b.ref_frame_stride, b.cur, b.cur_frame_stride, b.width, b.height, b.stride, range,
                        nbx_full, o);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -379,9 +377,9 @@ hipError_t launch_partition_search(const uint8_t* ref, size_t ref_frame_stride, 
   const int sx = fast ? nbx_full : 0, sy = fast ? nby_full : 0;
   const int n = fast ? (o.nbx - sx) * o.nby + sx * (o.nby - sy) : o.nbx * o.nby;
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(me_part_generic_kernel, dim3((unsigned)n, (unsigned)n_frames),
-                     dim3(GEN_THREADS), 0, stream, ref, ref_frame_stride, cur, cur_frame_stride,
-                     width, height, stride, blk, range, sx, sy, o);
+  hipLaunchKernelGGL(me_part_generic_kernel, dim3((unsigned)n, (unsigned)b.n_frames),
+                     dim3(GEN_THREADS), 0, stream, b.ref, b.ref_frame_stride, b.cur, b.cur_frame_stride,
+                     b.width, b.height, b.stride, b.blk, range, sx, sy, o);
   return hipGetLastError();
 }
 

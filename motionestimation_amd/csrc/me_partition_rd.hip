@@ -373,15 +373,13 @@ __global__ __launch_bounds__(PART_FAST_THREADS) void me_part_rd_fast_kernel(
 
 }  // namespace
 
-hipError_t launch_partition_rd_search(const uint8_t* ref, size_t ref_frame_stride,
-                                      const uint8_t* cur, size_t cur_frame_stride, int width,
-                                      int height, int stride, int blk, int range, uint32_t lambda,
-                                      int n_frames, bool fast, const int16_t* pred,
-                                      const me_part_rd_fields& out, hipStream_t stream) {
-  const int h = blk / 2;
-  const PartRdOut o{out, pred, (width + blk - 1) / blk, (height + blk - 1) / blk,
-                    (width + h - 1) / h, (height + h - 1) / h, lambda};
-  const int nbx_full = width / blk, nby_full = height / blk;
+hipError_t launch_partition_rd_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,
+                                      const int16_t* pred, const me_part_rd_fields& out,
+                                      hipStream_t stream) {
+  const int h = b.blk / 2;
+  const PartRdOut o{out, pred, (b.width + b.blk - 1) / b.blk, (b.height + b.blk - 1) / b.blk,
+                    (b.width + h - 1) / h, (b.height + h - 1) / h, lambda};
+  const int nbx_full = b.width / b.blk, nby_full = b.height / b.blk;
   if (fast) {
     const int rows = partition_rd_fast_rows(range), pitch = partition_fast_pitch(range);
     // window, current blocks, keys, then the rate tables (4 G + rows - 15 words
@@ -389,9 +387,9 @@ hipError_t launch_partition_rd_search(const uint8_t* ref, size_t ref_frame_strid
     const size_t lds = (size_t)((rows * pitch + 15) & ~15) + PART_TB * 256 + PART_TB * P_N * 8 +
                        (size_t)PART_TB * 4 * (4 * partition_fast_groups(range) + rows - 15);
     const dim3 grid((unsigned)((nbx_full + PART_TB - 1) / PART_TB), (unsigned)nby_full,
-                    (unsigned)n_frames);
+                    (unsigned)b.n_frames);
     hipLaunchKernelGGL(me_part_rd_fast_kernel<PART_RD_K>, grid, dim3(PART_FAST_THREADS), lds,
-                       stream, ref, ref_frame_stride, cur, cur_frame_stride, width, height, stride,
+                       stream, b.ref, b.ref_frame_stride, b.cur, b.cur_frame_stride, b.width, b.height, b.stride,
                        range, nbx_full, o);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -401,9 +399,9 @@ hipError_t launch_partition_rd_search(const uint8_t* ref, size_t ref_frame_strid
   const int sx = fast ? nbx_full : 0, sy = fast ? nby_full : 0;
   const int n = fast ? (o.nbx - sx) * o.nby + sx * (o.nby - sy) : o.nbx * o.nby;
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(me_part_rd_generic_kernel, dim3((unsigned)n, (unsigned)n_frames),
-                     dim3(GEN_THREADS), 0, stream, ref, ref_frame_stride, cur, cur_frame_stride,
-                     width, height, stride, blk, range, sx, sy, o);
+  hipLaunchKernelGGL(me_part_rd_generic_kernel, dim3((unsigned)n, (unsigned)b.n_frames),
+                     dim3(GEN_THREADS), 0, stream, b.ref, b.ref_frame_stride, b.cur, b.cur_frame_stride,
+                     b.width, b.height, b.stride, b.blk, range, sx, sy, o);
   return hipGetLastError();
 }
 

@@ -331,28 +331,26 @@ __global__ __launch_bounds__(RD_FAST_THREADS) void me_rd_fast_kernel(
 
 }  // namespace
 
-hipError_t launch_rd_search(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
-                            size_t cur_frame_stride, int width, int height, int stride, int blk,
-                            int range, uint32_t lambda, int n_frames, bool fast,
+hipError_t launch_rd_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,
                             const int16_t* pred, int16_t* mv, uint32_t* cost, uint32_t* dist,
                             uint8_t* bits, hipStream_t stream) {
-  const RdOut o{pred, mv, cost, dist, bits, (width + blk - 1) / blk, (height + blk - 1) / blk,
+  const RdOut o{pred, mv, cost, dist, bits, (b.width + b.blk - 1) / b.blk, (b.height + b.blk - 1) / b.blk,
                 lambda};
-  const int nbx_full = width / blk, nby_full = height / blk;
+  const int nbx_full = b.width / b.blk, nby_full = b.height / b.blk;
   if (fast) {
     const int rows = rd_fast_rows(range), pitch = rd_fast_pitch(range);
     // window, current blocks, keys, then the rate tables (4 G + rows - 15 words per block)
     const size_t lds = (size_t)((rows * pitch + 15) & ~15) + RD_TB * 256 + RD_TB * 8 +
                        (size_t)RD_TB * 4 * (4 * rd_fast_groups(range) + rows - 15);
     const dim3 grid((unsigned)((nbx_full + RD_TB - 1) / RD_TB), (unsigned)nby_full,
-                    (unsigned)n_frames);
+                    (unsigned)b.n_frames);
     if (rd_fast_k(range) == RD_K_SMALL)
       hipLaunchKernelGGL(me_rd_fast_kernel<RD_K_SMALL>, grid, dim3(RD_FAST_THREADS), lds, stream,
-                         ref, ref_frame_stride, cur, cur_frame_stride, width, height, stride,
+                         b.ref, b.ref_frame_stride, b.cur, b.cur_frame_stride, b.width, b.height, b.stride,
                          range, nbx_full, o);
     else
       hipLaunchKernelGGL(me_rd_fast_kernel<RD_K_LARGE>, grid, dim3(RD_FAST_THREADS), lds, stream,
-                         ref, ref_frame_stride, cur, cur_frame_stride, width, height, stride,
+                         b.ref, b.ref_frame_stride, b.cur, b.cur_frame_stride, b.width, b.height, b.stride,
                          range, nbx_full, o);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -362,9 +360,9 @@ hipError_t launch_rd_search(const uint8_t* ref, size_t ref_frame_stride, const u
   const int sx = fast ? nbx_full : 0, sy = fast ? nby_full : 0;
   const int n = fast ? (o.nbx - sx) * o.nby + sx * (o.nby - sy) : o.nbx * o.nby;
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(me_rd_generic_kernel, dim3((unsigned)n, (unsigned)n_frames),
-                     dim3(GEN_THREADS), 0, stream, ref, ref_frame_stride, cur, cur_frame_stride,
-                     width, height, stride, blk, range, sx, sy, o);
+  hipLaunchKernelGGL(me_rd_generic_kernel, dim3((unsigned)n, (unsigned)b.n_frames),
+                     dim3(GEN_THREADS), 0, stream, b.ref, b.ref_frame_stride, b.cur, b.cur_frame_stride,
+                     b.width, b.height, b.stride, b.blk, range, sx, sy, o);
   return hipGetLastError();
 }
 

@@ -787,13 +787,12 @@ int tile_of(int blk) { return blk <= 4 ? 4 : blk <= 8 ? 8 : blk <= 16 ? 16 : blk
 
 // cost: ME_COST_SSD, ME_COST_SAD or ME_COST_SATD (the callers reject the rest).
 template <int TB>
-void refine_tb(int cost, dim3 grid, hipStream_t stream, const uint8_t* ref, size_t rfs,
-               const uint8_t* cur, size_t cfs, int width, int height, int stride, int blk, int nbx,
-               int nblk, const int16_t* mv_in, int16_t* mv_out, uint32_t* cost_out) {
-#define ME_QPEL_REFINE_K(COST)                                                                  \
+void refine_tb(int cost, dim3 grid, hipStream_t stream, const FrameBatch& b, int nbx, int nblk,
+               const int16_t* mv_in, int16_t* mv_out, uint32_t* cost_out) {
+#define ME_QPEL_REFINE_K(COST)                                                                   \
   hipLaunchKernelGGL((me_qpel_refine_kernel<TB, COST>), grid, dim3(QpelGeom<TB>::NT), 0, stream, \
-                     ref, rfs, cur, cfs, width, height, stride, blk, nbx, nblk, mv_in, mv_out,  \
-                     cost_out)
+                     b.ref, b.ref_frame_stride, b.cur, b.cur_frame_stride, b.width, b.height,    \
+                     b.stride, b.blk, nbx, nblk, mv_in, mv_out, cost_out)
   if (cost == ME_COST_SSD)
     ME_QPEL_REFINE_K(ME_COST_SSD);
   else if (cost == ME_COST_SATD)
@@ -804,14 +803,14 @@ void refine_tb(int cost, dim3 grid, hipStream_t stream, const uint8_t* ref, size
 }
 
 template <int TB>
-void refine_rd_tb(int cost, dim3 grid, hipStream_t stream, const uint8_t* ref, size_t rfs,
-                  const uint8_t* cur, size_t cfs, int width, int height, int stride, int blk,
-                  int nbx, int nblk, uint32_t lambda, const int16_t* pred, const int16_t* mv_in,
-                  int16_t* mv_out, uint32_t* cost_out, uint32_t* dist_out) {
+void refine_rd_tb(int cost, dim3 grid, hipStream_t stream, const FrameBatch& b, int nbx, int nblk,
+                  uint32_t lambda, const int16_t* pred, const int16_t* mv_in, int16_t* mv_out,
+                  uint32_t* cost_out, uint32_t* dist_out) {
 #define ME_QPEL_REFINE_RD_K(COST)                                                               \
   hipLaunchKernelGGL((me_qpel_refine_rd_kernel<TB, COST>), grid, dim3(QpelGeom<TB>::NT), 0,     \
-                     stream, ref, rfs, cur, cfs, width, height, stride, blk, nbx, nblk, lambda, \
-                     pred, mv_in, mv_out, cost_out, dist_out)
+                     stream, b.ref, b.ref_frame_stride, b.cur, b.cur_frame_stride, b.width,     \
+                     b.height, b.stride, b.blk, nbx, nblk, lambda, pred, mv_in, mv_out,         \
+                     cost_out, dist_out)
   if (cost == ME_COST_SSD)
     ME_QPEL_REFINE_RD_K(ME_COST_SSD);
   else if (cost == ME_COST_SATD)
@@ -823,20 +822,17 @@ void refine_rd_tb(int cost, dim3 grid, hipStream_t stream, const uint8_t* ref, s
 
 }  // namespace
 
-hipError_t launch_qpel_refine_rd(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
-                                 size_t cur_frame_stride, int width, int height, int stride,
-                                 int blk, int cost, uint32_t lambda, int n_frames,
-                                 const int16_t* pred, const int16_t* mv_in, int16_t* mv_out,
-                                 uint32_t* cost_out, uint32_t* dist_out, hipStream_t stream) {
-  const int nbx = (width + blk - 1) / blk, nblk = nbx * ((height + blk - 1) / blk);
-  const dim3 grid((unsigned)nblk, (unsigned)n_frames);
+hipError_t launch_qpel_refine_rd(const FrameBatch& b, int cost, uint32_t lambda, const int16_t* pred,
+                                 const int16_t* mv_in, int16_t* mv_out, uint32_t* cost_out,
+                                 uint32_t* dist_out, hipStream_t stream) {
+  const int nbx = (b.width + b.blk - 1) / b.blk, nblk = nbx * ((b.height + b.blk - 1) / b.blk);
+  const dim3 grid((unsigned)nblk, (unsigned)b.n_frames);
 #define ME_QPEL_REFINE_RD(TB)                                                                   \
   case TB:                                                                                      \
-    refine_rd_tb<TB>(cost, grid, stream, ref, ref_frame_stride, cur, cur_frame_stride, width,   \
-                     height, stride, blk, nbx, nblk, lambda, pred, mv_in, mv_out, cost_out,     \
+    refine_rd_tb<TB>(cost, grid, stream, b, nbx, nblk, lambda, pred, mv_in, mv_out, cost_out,   \
                      dist_out);                                                                 \
     break
-  switch (tile_of(blk)) {
+  switch (tile_of(b.blk)) {
     ME_QPEL_REFINE_RD(4);
     ME_QPEL_REFINE_RD(8);
     ME_QPEL_REFINE_RD(16);
@@ -847,18 +843,15 @@ hipError_t launch_qpel_refine_rd(const uint8_t* ref, size_t ref_frame_stride, co
   return hipGetLastError();
 }
 
-hipError_t launch_qpel_refine(const uint8_t* ref, size_t ref_frame_stride, const uint8_t* cur,
-                              size_t cur_frame_stride, int width, int height, int stride, int blk,
-                              int cost, int n_frames, const int16_t* mv_in, int16_t* mv_out,
+hipError_t launch_qpel_refine(const FrameBatch& b, int cost, const int16_t* mv_in, int16_t* mv_out,
                               uint32_t* cost_out, hipStream_t stream) {
-  const int nbx = (width + blk - 1) / blk, nblk = nbx * ((height + blk - 1) / blk);
-  const dim3 grid((unsigned)nblk, (unsigned)n_frames);
+  const int nbx = (b.width + b.blk - 1) / b.blk, nblk = nbx * ((b.height + b.blk - 1) / b.blk);
+  const dim3 grid((unsigned)nblk, (unsigned)b.n_frames);
 #define ME_QPEL_REFINE(TB)                                                                      \
   case TB:                                                                                      \
-    refine_tb<TB>(cost, grid, stream, ref, ref_frame_stride, cur, cur_frame_stride, width,      \
-                  height, stride, blk, nbx, nblk, mv_in, mv_out, cost_out);                     \
+    refine_tb<TB>(cost, grid, stream, b, nbx, nblk, mv_in, mv_out, cost_out);                   \
     break
-  switch (tile_of(blk)) {
+  switch (tile_of(b.blk)) {
     ME_QPEL_REFINE(4);
     ME_QPEL_REFINE(8);
     ME_QPEL_REFINE(16);
@@ -890,19 +883,17 @@ hipError_t launch_qpel_compensate(const uint8_t* ref, const uint8_t* cur, int wi
   return hipGetLastError();
 }
 
-hipError_t launch_bipred(const uint8_t* ref0, size_t ref0_frame_stride, const uint8_t* ref1,
-                         size_t ref1_frame_stride, const uint8_t* cur, size_t cur_frame_stride,
-                         int width, int height, int stride, int blk, int cost, int refine,
-                         int n_frames, const int16_t* q0_in, const int16_t* q1_in, int16_t* q0_out,
-                         int16_t* q1_out, uint8_t* mode_out, uint32_t* cost_out,
+hipError_t launch_bipred(const FrameBatch& b, const uint8_t* ref1, size_t ref1_frame_stride,
+                         int cost, int refine, const int16_t* q0_in, const int16_t* q1_in,
+                         int16_t* q0_out, int16_t* q1_out, uint8_t* mode_out, uint32_t* cost_out,
                          uint32_t* cost3_out, hipStream_t stream) {
-  const int nbx = (width + blk - 1) / blk, nblk = nbx * ((height + blk - 1) / blk);
-  const dim3 grid((unsigned)nblk, (unsigned)n_frames);
+  const int nbx = (b.width + b.blk - 1) / b.blk, nblk = nbx * ((b.height + b.blk - 1) / b.blk);
+  const dim3 grid((unsigned)nblk, (unsigned)b.n_frames);
 #define ME_BIPRED_K(TB, COST)                                                                   \
   hipLaunchKernelGGL((me_bipred_kernel<TB, COST>), grid, dim3(QpelGeom<TB>::NT), 0, stream,     \
-                     ref0, ref0_frame_stride, ref1, ref1_frame_stride, cur, cur_frame_stride,   \
-                     width, height, stride, blk, nbx, nblk, refine, q0_in, q1_in, q0_out,       \
-                     q1_out, mode_out, cost_out, cost3_out)
+                     b.ref, b.ref_frame_stride, ref1, ref1_frame_stride, b.cur,                 \
+                     b.cur_frame_stride, b.width, b.height, b.stride, b.blk, nbx, nblk, refine, \
+                     q0_in, q1_in, q0_out, q1_out, mode_out, cost_out, cost3_out)
 #define ME_BIPRED(TB)                  \
   case TB:                             \
     if (cost == ME_COST_SSD)           \
@@ -912,7 +903,7 @@ hipError_t launch_bipred(const uint8_t* ref0, size_t ref0_frame_stride, const ui
     else                               \
       ME_BIPRED_K(TB, ME_COST_SAD);    \
     break
-  switch (tile_of(blk)) {
+  switch (tile_of(b.blk)) {
     ME_BIPRED(4);
     ME_BIPRED(8);
     ME_BIPRED(16);

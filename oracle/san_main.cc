@@ -20,7 +20,12 @@
 //   - the search dispatcher (me_dispatch.cpp) over the cases of
 //     tests/golden/plans/dispatch.json, from four threads at once (they share
 //     the plan cache of me_valu_plan.cpp): every block of every job in
-//     exactly one launch, through launch windows of several sizes.
+//     exactly one launch, through launch windows of several sizes;
+//   - the C ABI's argument rules and record layouts (me_api_rules.cpp): every
+//     case of tests/golden/api_args.json through its entry point's rules (the
+//     recorded status), then what no GPU recording can hold: every integer of
+//     every entry point at INT_MAX and INT_MIN, frame strides of SIZE_MAX, and
+//     the layouts of many shapes (regions back to back inside the total).
 // Exit status 0 and "san ok" on success; the sanitizers abort otherwise.
 #include <stdint.h>
 #include <stdio.h>
@@ -32,6 +37,9 @@
 #include <thread>
 #include <vector>
 
+#include <limits.h>
+
+#include "api_rules_cases.h"
 #include "dispatch_cases.h"
 #include "me.h"
 #include "me_geom.h"
@@ -472,6 +480,89 @@ static void dispatcher() {
   for (std::thread& t : th) t.join();
 }
 
+// Regions back to back, each aligned to its element, and the total the entry
+// points asked for before the layouts were functions.
+static void check_layout(const me::rules::Layout& L, size_t total) {
+  size_t end = 0;
+  for (int k = 0; k < L.n; k++) {
+    CHECK(L.off[k] == end && L.off[k] % L.elem[k] == 0 && L.bytes[k] % L.elem[k] == 0);
+    end += L.bytes[k];
+  }
+  CHECK(end <= total && L.total == total);
+}
+
+static void api_rules() {
+  FILE* f = fopen(API_ARGS_TABLE, "r");
+  CHECK(f != nullptr);
+  static char line[1 << 14];
+  char err[512];
+  ApiCase c;
+  std::vector<std::string> fns;
+  int cases = 0;
+  while (fgets(line, sizeof line, f)) {
+    if (!parse_api_case(line, &c)) continue;
+    cases++;
+    CHECK(run_api_case(c, c.ndev, err, sizeof err) == c.status && err[0]);
+    if (fns.empty() || fns.back() != c.fn) fns.push_back(c.fn);
+  }
+  fclose(f);
+  CHECK(cases > 500 && fns.size() > 25);
+  // wild values: refused or accepted, never an overflow or a wild read
+  int ApiCase::* const ints[] = {&ApiCase::width, &ApiCase::height, &ApiCase::stride, &ApiCase::blk,
+                                 &ApiCase::range, &ApiCase::cost, &ApiCase::n_frames, &ApiCase::refine,
+                                 &ApiCase::r0, &ApiCase::r1, &ApiCase::ref_row0, &ApiCase::cur_row0,
+                                 &ApiCase::num_blks};
+  long long ApiCase::* const sizes[] = {&ApiCase::fs_ref, &ApiCase::fs_cur, &ApiCase::fs_ref1};
+  for (const std::string& fn : fns)
+    for (int ndev : {1, 2}) {
+      ApiCase w;
+      w.fn = fn;
+      CHECK(run_api_case(w, ndev, err, sizeof err) >= 0);  // (a known entry point)
+      for (int v : {INT_MAX, INT_MIN, -INT_MAX}) {
+        for (auto m : ints) {
+          w = ApiCase{};
+          w.fn = fn;
+          w.*m = v;
+          (void)run_api_case(w, ndev, err, sizeof err);
+          w.r0 = w.r1 = v;  // ... and with the rows at the same end
+          (void)run_api_case(w, ndev, err, sizeof err);
+        }
+        w = ApiCase{};
+        w.fn = fn;
+        w.lambda = (uint32_t)v;
+        (void)run_api_case(w, ndev, err, sizeof err);
+      }
+      for (auto m : sizes)
+        for (int n_frames : {1, 2, 4096}) {
+          w = ApiCase{};
+          w.fn = fn;
+          w.n_frames = n_frames;
+          w.*m = -1;  // SIZE_MAX
+          const int s = run_api_case(w, ndev, err, sizeof err);
+          // where a stride that large is read (n_frames > 1), the stack is past 2 GiB
+          bool batched = false;
+          for (const char* b : {"me_full_search_batch_device", "me_refine_qpel_device", "me_bipred_device",
+                                "me_partition_search_device", "me_rd_search_device",
+                                "me_refine_qpel_rd_device", "me_partition_rd_search_device"})
+            batched |= fn == b;
+          if (n_frames > 1 && batched && (m != sizes[2] || fn == "me_bipred_device")) CHECK(s != ME_OK);
+        }
+    }
+  for (int t = 0; t < 2000; t++) {
+    const int W = 1 + (int)(next_u64() % 8000), H = 1 + (int)(next_u64() % 4400);
+    const int B = 2 * (1 + (int)(next_u64() % 32));
+    int n[4];
+    CHECK(me_partition_counts(W, H, B, n) == ME_OK);
+    const size_t nb = (size_t)me_num_blocks(W, H, B);
+    const size_t cells = (size_t)n[0] + n[1] + n[2] + n[3], n0 = (size_t)n[0];
+    check_layout(me::rules::layout_mv_cost(nb), 8 * nb);
+    check_layout(me::rules::layout_bipred(nb), 28 * nb);
+    check_layout(me::rules::layout_rd(nb), (17 * nb + 7) / 8 * 8);
+    check_layout(me::rules::layout_partition(n), (8 * cells + 5 * n0 + 7) / 8 * 8);
+    check_layout(me::rules::layout_partition_rd(n), (13 * cells + 9 * n0 + 7) / 8 * 8);
+  }
+}
+
 int main() {
   pool();
   planner();
@@ -479,6 +570,7 @@ int main() {
   valu_planners();
   mfma_planners();
   dispatcher();
+  api_rules();
   printf("san ok\n");
   return 0;
 }

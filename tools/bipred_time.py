@@ -100,6 +100,9 @@ def main():
     print(json.dumps({
         "tool": "bipred_time", "config": a.config, "width": w, "height": h, "block": blk,
         "range": span, "cost": a.cost, "frames_per_step": F, "steps": a.steps,
+        # each arm's spread over the steps (us per frame), next to the medians below
+        "us_per_frame_p10_p90": {k: [round(sorted(v)[int(q * a.steps)] * 1e3 / F, 2) for q in (0.1, 0.9)]
+                                 for k, v in ms.items()},
         "search_path": path,
         "search_us_per_frame": round(med["search"], 2),
         "search_refine_us_per_frame": round(med["search_refine"], 2),

@@ -101,6 +101,9 @@ def main():
     print(json.dumps({
         "tool": "rd_time", "config": a.config, "width": w, "height": h, "block": blk,
         "range": span, "cost": "sad", "lambda": a.lam, "frames_per_step": F, "steps": a.steps,
+        # each arm's spread over the steps (us per frame), next to the medians below
+        "us_per_frame_p10_p90": {k: [round(sorted(v)[int(q * a.steps)] * 1e3 / F, 2) for q in (0.1, 0.9)]
+                                 for k, v in ms.items()},
         "kernel_variant": {0: "generic", 1: "fast"}.get(variant, "rejected"),
         "full_us_per_frame": round(med["full"], 2),
         "rd_us_per_frame": round(med["rd"], 2),
