@@ -79,6 +79,7 @@ static Tuning read_tuning() {
   env_int("ME_PRUNE", 0, 2, &t.prune);
   env_int("ME_PRUNE_BYPASS", 0, 1, &t.prune_bypass);
   env_int("ME_PRUNE_PLANES", 0, 1, &t.prune_planes);
+  env_int("ME_PRUNE_SPLIT", 0, 1, &t.prune_split);
   t.prune_stats = 1;
   env_int("ME_MFMA_BATCH", 0, 1, &t.mfma_batch);
   env_int("ME_MFMA_S2K", 0, 1, &t.mfma_s2k);
@@ -795,6 +796,21 @@ extern "C" int me_debug_prune_stats(me_ctx* c, uint32_t* out4) {
   if (hipSetDevice(d.id) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
       hipMemcpy(out4, d.sched + me::SCHED_PRUNE, 16, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemset(d.sched + me::SCHED_PRUNE, 0, 16) != hipSuccess)
+    rc = ME_EDEVICE;
+  (void)hipSetDevice(prev);
+  return rc;
+}
+// ... and the executed wave-tasks of pruned launches by split class: run whole
+// (P = 1), with 2 and with 4 lanes per list entry (me_geom.h flow_split_parts).
+extern "C" int me_debug_prune_split_stats(me_ctx* c, uint32_t* out3) {
+  if (!c || c->devs.empty() || !out3) return ME_EINVAL;
+  Dev& d = c->devs[0];
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  int rc = ME_OK;
+  if (hipSetDevice(d.id) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(out3, d.sched + me::SCHED_SPLIT, 12, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemset(d.sched + me::SCHED_SPLIT, 0, 12) != hipSuccess)
     rc = ME_EDEVICE;
   (void)hipSetDevice(prev);
   return rc;

@@ -100,7 +100,34 @@ struct QsadGeom {
   int prune_stats;   // 1: live / total lane-tasks and bypassed items counted in sched[SCHED_PRUNE..]
   int prune_slots;   // ring slots when pruning (each slot carries FLOW_PRUNE_BYTES of bound scratch)
   int prune_lds;     // dynamic LDS bytes of the pruning launch
+  int prune_split;   // 1: a pruned item's short wave-task is split by dy rows (flow_split_* below)
 };
+
+// ---- row split of a pruned item's partial wave-task (me_flow_kernel) ----
+// A wave-task holding n <= 32 list entries runs with P lanes per entry: lane l
+// takes entry l / P and part l % P, the dy rows [row0, row0 + rows) of the
+// entry's K = 13 row chunk.  The parts overlap by a row where that saves the
+// row masks of an exact partition: a candidate computed twice gives the same key.
+constexpr int FLOW_SPLIT_K = 13;
+constexpr int flow_split_parts(int n) { return n <= 16 ? 4 : n <= 32 ? 2 : 1; }
+constexpr int flow_split_rows(int P) { return P == 4 ? 4 : P == 2 ? 7 : FLOW_SPLIT_K; }
+constexpr int flow_split_row0(int P, int s) { return P == 4 ? 3 * s : P == 2 ? 6 * s : 0; }
+constexpr bool flow_split_covers(int P) {  // the parts' union is rows 0..12, none past them
+  unsigned m = 0;
+  for (int s = 0; s < P; s++)
+    for (int j = 0; j < flow_split_rows(P); j++) {
+      if (flow_split_row0(P, s) + j >= FLOW_SPLIT_K) return false;
+      m |= 1u << (flow_split_row0(P, s) + j);
+    }
+  return m == (1u << FLOW_SPLIT_K) - 1;
+}
+constexpr bool flow_split_fits(int P) {  // every n mapped to P has its P * n lanes in the wave
+  for (int n = 1; n <= 64; n++)
+    if (flow_split_parts(n) == P && n * P > 64) return false;
+  return true;
+}
+static_assert(flow_split_covers(1) && flow_split_covers(2) && flow_split_covers(4), "parts cover rows 0..12");
+static_assert(flow_split_fits(1) && flow_split_fits(2) && flow_split_fits(4), "64 / P >= the largest n of P");
 
 // Bound scratch of one ring slot of the pruning flow kernel: four x-phase
 // planes of 77 rows x 32 box-sum bytes (the live list overlays them once the

@@ -25,6 +25,9 @@ constexpr int SCHED_ERR = 31;
 // since the words were last zeroed: live lane-tasks, all lane-tasks, items
 // whose bound was bypassed, items.
 constexpr int SCHED_PRUNE = 24;
+// ... and its executed wave-tasks run whole, with 2 and with 4 lanes per list
+// entry (the row split, me_geom.h flow_split_parts): three words.
+constexpr int SCHED_SPLIT = 28;
 
 // The packed key of a candidate: the unsigned minimum of keys is the smallest
 // cost and, among equal costs, the first displacement in raster order.

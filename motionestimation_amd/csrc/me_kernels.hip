@@ -946,10 +946,13 @@ struct FlowCtl {
   // pruning launches only (the plain launch's LDS ends above)
   uint32_t live[16];   // live lane-tasks of the slot's item (its list's length)
   uint32_t stats[4];   // tuning build: live, all lane-tasks, bypassed items, items (flushed at the end)
+  uint32_t split[3];   // tuning build: executed wave-tasks run with 1, 2, 4 lanes per list entry
 };
 // PF_PLANES: the launch has box-sum planes (FlowJobs::planes): the staging wave
 // DMAs an item's four planes with its window, and flow_bound skips its step 1.
-enum { PF_ON = 1, PF_VERIFY = 2, PF_BYPASS = 4, PF_STATS = 8, PF_PLANES = 16 };
+// PF_SPLIT: a pruned item's wave-task of <= 32 list entries is split by rows
+// (flow_split_task below).
+enum { PF_ON = 1, PF_VERIFY = 2, PF_BYPASS = 4, PF_STATS = 8, PF_PLANES = 16, PF_SPLIT = 32 };
 static_assert(sizeof(FlowCtl) <= FLOW_CTL_BYTES, "control block of the pruning launch");
 
 // Tile of the flow kernel's launch -> its item (all dy chunks: one pass).
@@ -1330,6 +1333,90 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
   }
 }
 
+// ------------------------------------------------ flow: the row-split wave-task
+// Task t of a pruned h = B item whose list has n <= 32 entries left for it
+// (almost every executed task of correlated content: 9 live lane-tasks of 320
+// per item on the bench input) would issue all 64 lanes' 13 dy rows for n live
+// ones.  Split by rows instead (me_geom.h flow_split_*): P = 4 or 2 lanes per
+// entry, lane l = entry l / P, part l % P, rows [j0, j0 + KP) of the entry's
+// chunk: 16 (KP + 15)-row window walks of 4 KP qsads instead of 52.  The parts'
+// keys meet in the block's keys word like those of different lane-tasks; rows
+// two parts share give the same key twice.  The fold column's candidate runs
+// in part 0 (j0 = 0: its row index is the chunk's).  A lane past the entries
+// repeats the last one (so it raises no edge mask of its own) and merges nothing.
+// The whole body, list read to key merge, lives here: nothing of it is live
+// across the unsplit task's K = 13 row loop.
+template <int B, int K, int PC, int P, typename Hook>
+__device__ __forceinline__ void flow_split_task(const SearchArgs& p, const QsadGeom& g, const Item& it,
+                                                const uint8_t* smem, const uint8_t* buf, uint32_t tile_off,
+                                                uint64_t* keys, int t, int n, int lc0c, int pfl,
+                                                Hook lag_check) {
+  constexpr int CW = B / 4, KP = flow_split_rows(P);
+  static_assert(K == FLOW_SPLIT_K && CW == 4, "the split's row rules");
+  const int S = p.range, G = g.groups;
+  const int lane = fresh_tid() & 63;
+  const int e = lane / P, j0 = flow_split_row0(P, lane & (P - 1));
+  const bool live = e < n;
+  const uint8_t* pv = buf + g.tile_bytes + g.tb * B * B;
+  const int i = (int)reinterpret_cast<const uint16_t*>(pv)[64 * t + (live ? e : n - 1)];
+  const int bg = (int)__umulhi((uint32_t)i, g.magic_groups);  // i / G
+  const int gi = i - bg * G;
+  const uint32_t magic_nb = 0xFFFFFFFFu / (uint32_t)it.nb + 1u;
+  const int lcr = it.nb == 1 ? bg : (int)__umulhi((uint32_t)bg, magic_nb);
+  const int b = bg - lcr * it.nb;
+  const int lc = lc0c + lcr;
+  const int d0 = lc * K + j0;  // dy + S of the lane's first row
+  const int tlx = (it.bx0 + b) * B;
+  const uint32_t* cur_lds = reinterpret_cast<const uint32_t*>(buf + g.tile_bytes);
+  uint32_t c[B][CW];
+#pragma unroll
+  for (int y = 0; y < B; y++) {
+    const uint4 v = reinterpret_cast<const uint4*>(cur_lds)[b * B + y];
+    c[y][0] = v.x; c[y][1] = v.y; c[y][2] = v.z; c[y][3] = v.w;
+  }
+  const int dymin = max(-S, -it.tly), dymax = min(S, p.height - it.h - it.tly);
+  const int dxmin = max(-S, -tlx), dxmax = min(S, p.width - B - tlx);
+  const int jlo = dymin + S - d0, jhi = dymax + S - d0;  // in the lane's rows
+  const bool full_rows = dymin + S <= 0 && dymax + S >= it.nch * K - 1;
+  const int w0 = (b * B) / 4 + gi;
+  uint64_t acc[KP];
+  const int jt = gi < K ? gi : K - 1;  // the fold candidate's row of the chunk
+  const uint32_t toff = tile_off + (uint32_t)((lc * K + jt) * g.pitch + b * B + 2 * S);
+  uint32_t tsad = 0;
+  qsad_lane<B, KP, B, PC, 4>(smem, g.pitch, tile_off, d0, w0, c, acc, lag_check);
+  if (g.fold) tsad = tail_sad<B, B>(smem, g.pitch, toff, c);
+  const int dxg = 4 * gi - S - it.a;
+  const bool edge = dxg < dxmin || dxg + 3 > dxmax;
+  uint32_t best;
+  if (full_rows && __builtin_amdgcn_ballot_w64(edge) == 0) {
+    best = lane_best<KP, false>(acc, 0u, 0u, jlo, jhi);
+  } else {
+    uint32_t mlo = 0, mhi = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int dx = dxg + k;
+      const uint32_t msk = (dx < dxmin || dx > dxmax) ? 0xFFFFu : 0u;
+      if (k < 2) mlo |= msk << (16 * k);
+      else mhi |= msk << (16 * (k - 2));
+    }
+    best = lane_best<KP, true>(acc, mlo, mhi, jlo, jhi);
+  }
+  if (g.fold) {
+    const bool tv = j0 == 0 && gi < K && jt >= jlo && jt <= jhi && S <= dxmax;
+    best = min(best, tv ? (tsad << 16) | (uint32_t)(5 * jt + 4) : ~0u);
+  }
+  if (live && best < 0xFFFF0000u) {
+    const int idx = (int)(best & 0xFFFFu), jj = idx / 5, k5 = idx - 5 * jj;
+    const int dy = d0 + jj - S, dx = k5 == 4 ? S : 4 * gi + k5 - S - it.a;
+    atomicMin(reinterpret_cast<unsigned long long*>(&keys[b]),
+              (unsigned long long)make_key(best >> 16, dx, dy));
+    // Verify mode (see the unsplit task): per lane, by the entry's index.
+    if ((pfl & PF_VERIFY) && pv[640 + i] && (best >> 16) <= reinterpret_cast<const uint32_t*>(pv + 960)[b] &&
+        p.sched)
+      __hip_atomic_store(p.sched + SCHED_ERR, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 template <int B, int K, int PC>
 __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g, FlowJobs jb) {
   static_assert(B == 16, "cur-block DMA layout of stage_item_wave");
@@ -1365,11 +1452,13 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       if (prune) ctl->live[tid] = 0;
     }
     if (prune && tid >= 32 && tid < 36) ctl->stats[tid - 32] = 0;
+    if (prune && tid >= 36 && tid < 39) ctl->split[tid - 36] = 0;
     if (tid == 16) {
       ctl->run = 0;
       ctl->pflags = !prune ? 0u
                            : (uint32_t)(PF_ON | (g.prune == 2 ? PF_VERIFY : 0) | (g.prune_bypass ? PF_BYPASS : 0) |
-                                        (g.prune_stats ? PF_STATS : 0) | (jb.planes ? PF_PLANES : 0));
+                                        (g.prune_stats ? PF_STATS : 0) | (jb.planes ? PF_PLANES : 0) |
+                                        (g.prune_split ? PF_SPLIT : 0));
     }
   }
   for (int i = tid; i < NB * g.tb; i += (int)blockDim.x) keys[i] = ~0ull;
@@ -1406,6 +1495,8 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
   unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_first = 0, st_spin = 0, st_n = 0;
   const unsigned long long st_r0 = __builtin_amdgcn_s_memrealtime();
   unsigned long long st_dma = 0, st_bound = 0, st_nb = 0;  // refills: DMA wait, bound phase, count
+  // executed wave-tasks run with 1, 2, 4 lanes per list entry: count << 40 | cycles (list read to key merge)
+  unsigned long long st_k1 = 0, st_k2 = 0, st_k4 = 0;
 #endif
   for (;;) {
     const int pfl = PC == 144 ? __builtin_amdgcn_readfirstlane((int)ctl->pflags) : 0;
@@ -1467,37 +1558,6 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     // slot's list; a task past the list only counts itself done.
     const int nlive = pfl ? __builtin_amdgcn_readfirstlane((int)ctl->live[slot]) : valid_lanes;
     if (64 * t < nlive) {
-    const bool live = 64 * t + lane < nlive;
-    const uint16_t* llist = reinterpret_cast<const uint16_t*>(buf + g.tile_bytes + g.tb * B * B);
-    const int i = pfl && live ? (int)llist[64 * t + lane] : 64 * t + lane;
-    const int ii = live ? i : 0;
-    const int bg = (int)__umulhi((uint32_t)ii, g.magic_groups);  // ii / G
-    const int gi = ii - bg * G;
-    const uint32_t magic_nb = 0xFFFFFFFFu / (uint32_t)it.nb + 1u;
-    const int lcr = it.nb == 1 ? bg : (int)__umulhi((uint32_t)bg, magic_nb);
-    const int b = bg - lcr * it.nb;
-    const int lc = lc0c + lcr;
-    const int d0 = lc * K;
-    const int tlx = (it.bx0 + b) * B;
-    uint32_t c[B][CW];
-#pragma unroll
-    for (int y = 0; y < B; y++) {
-      if constexpr (CW == 4) {
-        const uint4 v = reinterpret_cast<const uint4*>(cur_lds)[b * B + y];
-        c[y][0] = v.x; c[y][1] = v.y; c[y][2] = v.z; c[y][3] = v.w;
-      } else {
-        const uint2 v = reinterpret_cast<const uint2*>(cur_lds)[b * B + y];
-        c[y][0] = v.x; c[y][1] = v.y;
-      }
-    }
-    const int dxmin = max(-S, -tlx), dxmax = min(S, p.width - B - tlx);
-    const int jlo = dymin + S - d0, jhi = dymax + S - d0;
-    const bool full_rows = dymin + S <= 0 && dymax + S >= it.nch * K - 1;
-    const int w0 = (b * B) / 4 + gi;
-    uint64_t acc[K];
-    const int jt = gi < K ? gi : K - 1;
-    const uint32_t toff = tile_off + (uint32_t)((lc * K + jt) * g.pitch + b * B + 2 * S);
-    uint32_t tsad = 0;
     // Fairness: the SIMD arbiter issues the oldest waves first, so a young
     // wave's wave-task lags while older waves run through later items (single
     // 1080p frames: per SIMD one wave ran ~6 wave-tasks, two ran 1 each), and
@@ -1530,6 +1590,54 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
           "s_setprio 1\n"
           "2:" ::"s"(nx), "s"(lim1), "s"(lim2) : "scc");
     };
+    // The task's class: 0 runs whole (below), 1 / 2 split by rows over 2 / 4
+    // lanes per list entry (flow_split_task; pruned h = B items only: an
+    // h = B/2 item's list is full).
+    int cls = 0;
+#ifdef ME_STAMPS
+    const unsigned long long st_k0 = __builtin_amdgcn_s_memtime();
+#endif
+    if constexpr (PC == 144) {
+      const int n = nlive - 64 * t;
+      if ((pfl & PF_SPLIT) && it.h == B && n <= 32) cls = flow_split_parts(n) >> 1;
+      if ((pfl & PF_STATS) && lane == 0) atomicAdd(&ctl->split[cls], 1u);
+      if (cls == 2)
+        flow_split_task<B, K, PC, 4>(p, g, it, smem, buf, tile_off, keys + slot * g.tb, t, n, lc0c, pfl, lag_check);
+      else if (cls == 1)
+        flow_split_task<B, K, PC, 2>(p, g, it, smem, buf, tile_off, keys + slot * g.tb, t, n, lc0c, pfl, lag_check);
+    }
+    if (cls == 0) {
+    const bool live = 64 * t + lane < nlive;
+    const uint16_t* llist = reinterpret_cast<const uint16_t*>(buf + g.tile_bytes + g.tb * B * B);
+    const int i = pfl && live ? (int)llist[64 * t + lane] : 64 * t + lane;
+    const int ii = live ? i : 0;
+    const int bg = (int)__umulhi((uint32_t)ii, g.magic_groups);  // ii / G
+    const int gi = ii - bg * G;
+    const uint32_t magic_nb = 0xFFFFFFFFu / (uint32_t)it.nb + 1u;
+    const int lcr = it.nb == 1 ? bg : (int)__umulhi((uint32_t)bg, magic_nb);
+    const int b = bg - lcr * it.nb;
+    const int lc = lc0c + lcr;
+    const int d0 = lc * K;
+    const int tlx = (it.bx0 + b) * B;
+    uint32_t c[B][CW];
+#pragma unroll
+    for (int y = 0; y < B; y++) {
+      if constexpr (CW == 4) {
+        const uint4 v = reinterpret_cast<const uint4*>(cur_lds)[b * B + y];
+        c[y][0] = v.x; c[y][1] = v.y; c[y][2] = v.z; c[y][3] = v.w;
+      } else {
+        const uint2 v = reinterpret_cast<const uint2*>(cur_lds)[b * B + y];
+        c[y][0] = v.x; c[y][1] = v.y;
+      }
+    }
+    const int dxmin = max(-S, -tlx), dxmax = min(S, p.width - B - tlx);
+    const int jlo = dymin + S - d0, jhi = dymax + S - d0;
+    const bool full_rows = dymin + S <= 0 && dymax + S >= it.nch * K - 1;
+    const int w0 = (b * B) / 4 + gi;
+    uint64_t acc[K];
+    const int jt = gi < K ? gi : K - 1;
+    const uint32_t toff = tile_off + (uint32_t)((lc * K + jt) * g.pitch + b * B + 2 * S);
+    uint32_t tsad = 0;
     if (it.h == B) {
       qsad_lane<B, K, B, PC, 4>(smem, g.pitch, tile_off, lc * K, w0, c, acc, lag_check);
       if (g.fold) tsad = tail_sad<B, B>(smem, g.pitch, toff, c);
@@ -1572,6 +1680,15 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
           __hip_atomic_store(p.sched + SCHED_ERR, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
+    }
+#ifdef ME_STAMPS
+    {  // executed wave-tasks per class: count << 40 | cycles
+      const unsigned long long dt = (1ull << 40) + (__builtin_amdgcn_s_memtime() - st_k0);
+      st_k1 += cls == 0 ? dt : 0;
+      st_k2 += cls == 1 ? dt : 0;
+      st_k4 += cls == 2 ? dt : 0;
+    }
+#endif
     }
     // this wave-task is done; the last one of the item writes and refills the slot
     uint32_t prev = 0;
@@ -1627,6 +1744,7 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     if ((__builtin_amdgcn_readfirstlane((int)ctl->pflags) & PF_STATS) && p.sched) {
       __syncthreads();
       if (tid < 4) atomicAdd(p.sched + SCHED_PRUNE + tid, ctl->stats[tid]);
+      if (tid >= 4 && tid < 7) atomicAdd(p.sched + SCHED_SPLIT + tid - 4, ctl->split[tid - 4]);
     }
   }
 #ifdef ME_STAMPS
@@ -1636,8 +1754,11 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     unsigned long long* o = g_stamps + 8 * fw;
     o[0] = st_t0; o[1] = st_first; o[2] = __builtin_amdgcn_s_memtime(); o[3] = st_spin;
     o[4] = st_n; o[5] = st_r0; o[6] = __builtin_amdgcn_s_memrealtime(); o[7] = hw;
-    if (fw < (1 << 14)) {  // per wave, refills: [DMA wait cycles, bound cycles, refills]
+    // per wave, refills: [DMA wait cycles, bound cycles, refills]; executed
+    // wave-tasks by class: [whole, 2, 4 lanes per entry] as count << 40 | cycles
+    if (fw < (1 << 14)) {
       g_wstamps[8 * fw] = st_dma; g_wstamps[8 * fw + 1] = st_bound; g_wstamps[8 * fw + 2] = st_nb;
+      g_wstamps[8 * fw + 3] = st_k1; g_wstamps[8 * fw + 4] = st_k2; g_wstamps[8 * fw + 5] = st_k4;
     }
   }
 #endif

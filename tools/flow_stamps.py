@@ -3,7 +3,9 @@
 (libme_hip_stamps.so): start-up delay to the first task, time spent waiting for
 items, tasks per wave, and how the waves / CUs finish.  Diagnostic only (the
 stamps cost cycles themselves); times in shader cycles unless marked.
-usage: python3 tools/flow_stamps.py [r0:r1 (one stripe's block rows: the split mode)]"""
+The stamps library carries the tuning build's overrides (me_tuning.h), so e.g.
+ME_PRUNE_SPLIT=0 gives the wave-task durations without the row split.
+usage: python3 tools/flow_stamps.py [r0:r1 (one stripe's block rows: the split mode) | batchF]"""
 import os, sys
 import numpy as np
 import torch
@@ -113,3 +115,8 @@ nref = ws[:, 2].sum()
 if nref:
     print(f"refills {nref}: DMA wait mean {ws[:, 0].sum() / nref:.0f} cycles, stage-to-publish after it "
           f"(bound phase) mean {ws[:, 1].sum() / nref:.0f} cycles; spin per task mean {spin.sum() / max(ntask.sum(), 1):.0f}")
+    # Executed wave-tasks (list read to key merge) by row-split class: run
+    # whole, with 2 and with 4 lanes per list entry; word = count << 40 | cycles.
+    for col, name in ((3, "whole"), (4, "2 lanes/entry"), (5, "4 lanes/entry")):
+        cnt, cyc = (ws[:, col] >> 40).sum(), (ws[:, col] & ((1 << 40) - 1)).sum()
+        print(f"executed wave-tasks {name}: {cnt}" + (f", mean {cyc / cnt:.0f} cycles" if cnt else ""))

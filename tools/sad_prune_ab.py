@@ -12,9 +12,9 @@ a file name in motionestimation_amd/lib (ME_HIP_LIB), e.g. a build of the
 parent commit copied there as libme_hip_parent.so.  Per (input, library): the
 median and min-max of the per-call time over the rounds, and whether every
 library's fields are equal array for array.  A tuning build
-(libme_hip_tune.so; ME_PRUNE, ME_PRUNE_BYPASS, ME_FLOW_SLOTS, ME_FAIR_T pass
-through from the environment) also reports its live lane-task fraction and
-bypassed items per call.
+(libme_hip_tune.so; ME_PRUNE, ME_PRUNE_BYPASS, ME_PRUNE_SPLIT, ME_FLOW_SLOTS,
+ME_FAIR_T pass through from the environment) also reports its live lane-task
+fraction, bypassed items and executed wave-tasks by row-split class per call.
 usage: python3 tools/sad_prune_ab.py --libs libme_hip_parent.so,libme_hip.so [--rounds 5]
        [--inputs synth,foreman,noise] [--ms 300]"""
 import argparse
@@ -76,11 +76,19 @@ def child(a):
         L.me_debug_prune_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
         out = (ctypes.c_uint32 * 4)()
         L.me_debug_prune_stats(eng._h, out)  # zero the counts
+        split = hasattr(L, "me_debug_prune_split_stats")
+        out3 = (ctypes.c_uint32 * 3)()
+        if split:
+            L.me_debug_prune_split_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+            L.me_debug_prune_split_stats(eng._h, out3)
         run()
         torch.cuda.synchronize()
         L.me_debug_prune_stats(eng._h, out)
         stats = {"live": out[0], "total": out[1], "bypassed_items": out[2], "items": out[3],
                  "live_frac": out[0] / out[1] if out[1] else None}
+        if split:  # executed wave-tasks run whole / with 2 / with 4 lanes per list entry
+            L.me_debug_prune_split_stats(eng._h, out3)
+            stats["tasks_p1_p2_p4"] = list(out3)
     reps = 0
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
