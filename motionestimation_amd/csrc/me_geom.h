@@ -198,6 +198,38 @@ struct FlowJobs {
   int plane_rows[MAX_JOBS];
 };
 
+// ---- launch tile -> job ----
+// The rule: tile t belongs to the smallest j with tile_pre[j + 1] > t (a job
+// without tiles owns none), clamped to [0, n - 1].  Two forms of it, neither
+// with a trip count that grows with j (the kernels read the table from scalar
+// memory: every step is a dependent round trip):
+//   flow_job_from  the scan from a job j0 <= the tile's job.  A flow workgroup
+//                  walks its band's tiles upwards, so the job of its previous
+//                  item is such a j0 and the scan steps once per job boundary
+//                  between the two tiles.  From j0 = 0 it is the plain scan.
+//   flow_job_find  the bisection of the table (at most 5 steps for MAX_JOBS
+//                  jobs) where no earlier job is known.
+#if defined(__HIPCC__)
+#define ME_HOST_DEVICE __host__ __device__
+#else
+#define ME_HOST_DEVICE
+#endif
+ME_HOST_DEVICE inline int flow_job_from(const FlowJobs& jb, int tile, int j0) {
+  int j = j0;
+  while (j + 1 < jb.n && jb.tile_pre[j + 1] <= tile) j++;
+  return j;
+}
+ME_HOST_DEVICE inline int flow_job_find(const FlowJobs& jb, int tile) {
+  int lo = 0, hi = jb.n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (jb.tile_pre[mid + 1] > tile) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+#undef ME_HOST_DEVICE
+
 // ---- box-sum planes of the pruning flow plan (S = 32, 4-block tiles) ----
 // Per job, per resident ref row y (relative to ref_row0), four x-phase rows of
 // flow_plane_pitch bytes: row 4 y + k, byte i holds q(y, 4 i + k - 32).  The x

@@ -548,6 +548,21 @@ __device__ __forceinline__ Item item_of(const SearchArgs& p, const QsadGeom& g, 
 // Tile of a launch over a job table -> (job, tile of that job's rows): jobs
 // are consecutive tile ranges (jb.tile_pre), every job the same frame
 // geometry; a job's planes and records are its own.
+// job_item_at: j is the tile's job (flow_job_from / flow_job_find of me_geom.h).
+template <int B, int K>
+__device__ __forceinline__ Item job_item_at(const SearchArgs& p, const QsadGeom& g,
+                                            const FlowJobs& jb, int tile, int pass, int j) {
+  QsadGeom gj = g;
+  gj.row0 = jb.r0[j];
+  if (g.strip_w > 0) gj.nrows = (jb.tile_pre[j + 1] - jb.tile_pre[j]) / g.wg_per_row;  // strip walk
+  Item it = item_of<B, K>(p, gj, tile - jb.tile_pre[j], pass);
+  it.j = j;
+  return it;
+}
+// The item kernel claims its tiles dynamically and in no order: the scan from
+// job 0.  (flow_job_from's loop and job_item_at's body written out: through
+// either helper every me_fast_kernel instance allocated its registers anew,
+// and its items are long enough to hide the scan.)
 template <int B, int K>
 __device__ __forceinline__ Item job_item(const SearchArgs& p, const QsadGeom& g,
                                          const FlowJobs& jb, int tile, int pass) {
@@ -955,11 +970,17 @@ struct FlowCtl {
 enum { PF_ON = 1, PF_VERIFY = 2, PF_BYPASS = 4, PF_STATS = 8, PF_PLANES = 16, PF_SPLIT = 32 };
 static_assert(sizeof(FlowCtl) <= FLOW_CTL_BYTES, "control block of the pruning launch");
 
-// Tile of the flow kernel's launch -> its item (all dy chunks: one pass).
+// Tile of the flow kernel's launch -> its item (all dy chunks: one pass).  A
+// workgroup's tiles only grow (band0 + m + k n_x), so an item's job is found
+// from the job jprev of an earlier item of the workgroup; the first lookup of
+// a wave (jprev < 0) bisects the table.  The scan from job 0 this replaces made
+// one scalar-memory round trip per job in front of the tile, at every advance
+// and in front of every refill's DMA.
 template <int B, int K>
 __device__ __forceinline__ Item flow_item(const SearchArgs& p, const QsadGeom& g,
-                                          const FlowJobs& jb, int tile) {
-  return job_item<B, K>(p, g, jb, tile, 0);
+                                          const FlowJobs& jb, int tile, int jprev) {
+  const int j = jprev < 0 ? flow_job_find(jb, tile) : flow_job_from(jb, tile, jprev);
+  return job_item_at<B, K>(p, g, jb, tile, 0, j);
 }
 
 // Single-wave LDS DMA of one flow item (the aligned path): tile rows and cur
@@ -1472,7 +1493,7 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     // profiles/r02ae_ab_flow_start.txt).
     for (int i = 0; i < wave; i++) __builtin_amdgcn_s_sleep(10);
     if (g.prio) __builtin_amdgcn_s_setprio(3);  // see me_fast_kernel
-    const Item it0 = flow_item<B, K>(p, g, jb, tile_of(wave));
+    const Item it0 = flow_item<B, K>(p, g, jb, tile_of(wave), -1);
     const bool pl0 = stage_item_wave<B, PC == 144>(p, g, it0, smem + wave * slot_bytes, jb, ctl);
     if (g.prio) __builtin_amdgcn_s_setprio(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1497,6 +1518,17 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
   unsigned long long st_dma = 0, st_bound = 0, st_nb = 0;  // refills: DMA wait, bound phase, count
   // executed wave-tasks run with 1, 2, 4 lanes per list entry: count << 40 | cycles (list read to key merge)
   unsigned long long st_k1 = 0, st_k2 = 0, st_k4 = 0;
+  // the tile -> item decode (flow_item) at the advance and at the refill: count << 40 | cycles
+  unsigned long long st_da = 0, st_dr = 0;
+#define ME_DECODE_T0 const unsigned long long st_i0 = __builtin_amdgcn_s_memtime()
+#define ME_DECODE_T1(acc, item)                                                   \
+  do {                                                                            \
+    asm volatile("" ::"s"((item).j), "s"((item).by), "s"((item).bx0));            \
+    (acc) += (1ull << 40) + (__builtin_amdgcn_s_memtime() - st_i0);               \
+  } while (0)
+#else
+#define ME_DECODE_T0
+#define ME_DECODE_T1(acc, item)
 #endif
   for (;;) {
     const int pfl = PC == 144 ? __builtin_amdgcn_readfirstlane((int)ctl->pflags) : 0;
@@ -1505,7 +1537,9 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
     // advance to the item holding task q (pulls are in order: kc only grows)
     if (!have && kc < nitems) {
-      itc = flow_item<B, K>(p, g, jb, tile_of(kc));
+      ME_DECODE_T0;
+      itc = flow_item<B, K>(p, g, jb, tile_of(kc), -1);
+      ME_DECODE_T1(st_da, itc);
       nwc = flow_tasks<B, K>(p, g, itc, &lc0c);
       have = true;
     }
@@ -1513,7 +1547,9 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       basec += nwc;
       kc++;
       if (kc < nitems) {
-        itc = flow_item<B, K>(p, g, jb, tile_of(kc));
+        ME_DECODE_T0;
+        itc = flow_item<B, K>(p, g, jb, tile_of(kc), itc.j);  // (kc grew: its job did not fall)
+        ME_DECODE_T1(st_da, itc);
         nwc = flow_tasks<B, K>(p, g, itc, &lc0c);
       }
     }
@@ -1710,7 +1746,9 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       const int kn = kc + NB;
       if (kn < nitems) {
         if (g.prio) __builtin_amdgcn_s_setprio(3);
-        const Item itn = flow_item<B, K>(p, g, jb, tile_of(kn));
+        ME_DECODE_T0;
+        const Item itn = flow_item<B, K>(p, g, jb, tile_of(kn), it.j);  // (kn > kc)
+        ME_DECODE_T1(st_dr, itn);
 #ifdef ME_STAMPS
         const unsigned long long st_d0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1755,13 +1793,17 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     o[0] = st_t0; o[1] = st_first; o[2] = __builtin_amdgcn_s_memtime(); o[3] = st_spin;
     o[4] = st_n; o[5] = st_r0; o[6] = __builtin_amdgcn_s_memrealtime(); o[7] = hw;
     // per wave, refills: [DMA wait cycles, bound cycles, refills]; executed
-    // wave-tasks by class: [whole, 2, 4 lanes per entry] as count << 40 | cycles
+    // wave-tasks by class: [whole, 2, 4 lanes per entry] as count << 40 | cycles;
+    // flow_item decodes at [the advance, the refill] likewise
     if (fw < (1 << 14)) {
       g_wstamps[8 * fw] = st_dma; g_wstamps[8 * fw + 1] = st_bound; g_wstamps[8 * fw + 2] = st_nb;
       g_wstamps[8 * fw + 3] = st_k1; g_wstamps[8 * fw + 4] = st_k2; g_wstamps[8 * fw + 5] = st_k4;
+      g_wstamps[8 * fw + 6] = st_da; g_wstamps[8 * fw + 7] = st_dr;
     }
   }
 #endif
+#undef ME_DECODE_T0
+#undef ME_DECODE_T1
 }
 
 // ------------------------------------------------- flow: the box-sum prepass

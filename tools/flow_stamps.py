@@ -12,7 +12,10 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from motionestimation_amd import _lib, synth
-_lib.LIB_PATH = os.path.join(REPO, "motionestimation_amd", "lib", "libme_hip_stamps.so")
+# FLOW_STAMPS_LIB: another stamps build in motionestimation_amd/lib (e.g. one of
+# the parent commit's kernels, for the "before" of a kernel change)
+_lib.LIB_PATH = os.path.join(REPO, "motionestimation_amd", "lib",
+                             os.path.basename(os.environ.get("FLOW_STAMPS_LIB", "libme_hip_stamps.so")))
 import ctypes
 import motionestimation_amd as me
 
@@ -120,3 +123,18 @@ if nref:
     for col, name in ((3, "whole"), (4, "2 lanes/entry"), (5, "4 lanes/entry")):
         cnt, cyc = (ws[:, col] >> 40).sum(), (ws[:, col] & ((1 << 40) - 1)).sum()
         print(f"executed wave-tasks {name}: {cnt}" + (f", mean {cyc / cnt:.0f} cycles" if cnt else ""))
+    # Per XCD: the tile -> item decode (flow_item: the job lookup and the item's
+    # geometry) where a wave advances to its next item and where the refill
+    # names the item it stages, beside what a refill and a task wait for.
+    # ws and the wave records are both indexed workgroup * 16 + wave.
+    MASK = (1 << 40) - 1
+    full = buf.reshape(-1, 8)[:4096].astype(np.int64)
+    wxcd = (np.arange(4096) // 16) % 8
+    print("  per XCD: decode cycles per item at the advance / at the refill; per refill DMA wait, bound; spin per task")
+    for x in range(8):
+        sx = (wxcd == x) & (full[:, 0] > 0)
+        adv_n, adv_c = (ws[sx, 6] >> 40).sum(), (ws[sx, 6] & MASK).sum()
+        ref_n, ref_c = (ws[sx, 7] >> 40).sum(), (ws[sx, 7] & MASK).sum()
+        nr, nt = max(ws[sx, 2].sum(), 1), max(full[sx, 4].sum(), 1)
+        print(f"  XCD {x}: advance {adv_c / max(adv_n, 1):.0f} ({adv_n} items), refill {ref_c / max(ref_n, 1):.0f} ({ref_n}); "
+              f"DMA wait {ws[sx, 0].sum() / nr:.0f}, bound {ws[sx, 1].sum() / nr:.0f}; spin {full[sx, 3].sum() / nt:.0f}")
