@@ -826,6 +826,99 @@ me_status me_partition_rd_search(me_ctx* ctx, const uint8_t* ref, const uint8_t*
                                  me_cost cost, uint32_t lambda, const int16_t* pred_q,
                                  const me_part_rd_fields* out);
 
+/* ---- partition-wise quarter-pel refinement with sub-pel mode decision ----
+ * Takes the four integer grids of a partition search to quarter-pel, each of
+ * the nine partitions of a macroblock refined as one rectangle under J = cost +
+ * lambda * bits, and decides the mode again on the refined J.  No reference
+ * counterpart; parity is against the numpy restatement
+ * tests/partition_qpel_ref.py.  Grids, partitions, storage order, clipping and
+ * the leaf field are those of "partition search"; samples, stages, candidate
+ * order, the carried centre and strict < are those of "quarter-pel
+ * refinement"; bits(v), the predictor units and the one-predictor-per-macroblock
+ * rule are those of "rate-constrained partition search".  On top of them (exact
+ * integers; DESIGN.md "Partition-wise quarter-pel refinement"):
+ *   - input: the four integer vector grids mv_2nx2n, mv_2nxn, mv_nx2n, mv_nxn
+ *     of a me_part_fields; nothing else of the struct is read.  Any integer
+ *     fields are legal, not only a search's output; precondition |component|
+ *     <= ME_QPEL_MAX_MV (checked by the host call; the device call reads inside
+ *     the planes for any int16 but 4 m +- 3 must fit int16).
+ *   - refinement of a cell: each non-empty partition p of macroblock b is a
+ *     rectangle (x, y, w, h) clipped to the frame with integer vector m_p.  It
+ *     is refined by me_refine_qpel_rd's procedure on that rectangle: start at
+ *     4 m_p, stage 1 the eight neighbours at step 2, stage 2 the eight
+ *     neighbours of stage 1's winner at step 1, each in raster order, the
+ *     centre carried, a candidate replacing the best only if strictly smaller,
+ *     on Jq_p(q) = cost_p(P(q)) + lambda * (bits(qx - px_b) + bits(qy - py_b)).
+ *     cost is SAD, SSD or SATD over the rectangle's pixels only; SATD tiles are
+ *     anchored at the partition's top-left (partition offsets are multiples of
+ *     h >= 4, so these are the macroblock-anchored tiles too).
+ *   - output per cell of each grid: the quarter-pel vector, cost = Jq_p, dist =
+ *     cost_p at the result, bits = the result's rate as one byte (|q - p| <=
+ *     4 * 8000 + 3 + 32,768: 33 bits per component, R <= 66).
+ *   - mode: J(m) = sum of Jq_p over the non-empty partitions of shape m +
+ *     lambda * mbits(m), mbits = (1, 3, 3, 5).  Modes are tried in the order
+ *     0, 1, 2, 3 and a later one replaces the best only if strictly smaller.
+ *     mode: one byte per macroblock; mode_cost: J(mode) as u32.
+ *   - limits: lambda <= ME_PART_RD_MAX_LAMBDA, which keeps J below 2^32 for SSD
+ *     at B = 32 (66,585,600 + 269 * 2^23 = 2,323,121,152); a larger lambda
+ *     returns ME_EINVAL.  B in {8, 16, 32} (others ME_EUNSUPPORTED);
+ *     ME_COST_SSIM returns ME_EUNSUPPORTED; whole frames on the context's first
+ *     device only (several devices or repeated ids: ME_EUNSUPPORTED); stride *
+ *     height < 2^31.
+ *   - identities: (Q1) the 2Nx2N records (vector, J, dist) are
+ *     me_refine_qpel_rd's at block size B on mv_2nx2n with the same predictor,
+ *     bit for bit, for every cost.  (Q2) The NxN records of every cell, clipped
+ *     ones included, are me_refine_qpel_rd's at block size h on mv_nxn with
+ *     each macroblock's predictor repeated over its four quarters.  (Q3) With
+ *     lambda = 0, cost == dist and the 2Nx2N and NxN vectors are
+ *     me_refine_qpel's.  (Q4) mode and mode_cost follow from the cost arrays
+ *     alone by the mode rule.  (Q5) With the leaf field of the output
+ *     compensated by me_compensate_planes_qpel at B/2, at ME_COST_SAD
+ *     sum |mc - cur| = sum over the macroblocks of the dist of the chosen
+ *     mode's partitions: a prediction sample depends only on the pixel and the
+ *     vector, so a partition's vector repeated over its cells reproduces the
+ *     partition's prediction.  (Q6) Every cell's J is at most the J of its own
+ *     centre 4 m_p. */
+
+/* Refine n_frames >= 1 whole frames on HBM-resident planes of ctx's first
+ * device; layout and batching are me_partition_rd_search_device's (frame f's
+ * planes at + f * frame stride, its records at each pointer + f * that grid's
+ * count, its predictors at d_pred_q + 2 * f * nbx * nby, NULL: all zero).
+ * d_in and d_out are HOST structs of device pointers, read before the call
+ * returns.  d_out->f.mv_* and d_out->f.mode are required, everything else of
+ * d_out may be NULL.  In place (d_out->f.mv_x == d_in->mv_x) is allowed: a
+ * workgroup reads its macroblock's records before it writes them and every cell
+ * belongs to exactly one macroblock.  Asynchronous on `stream`, ordered like a
+ * search; uses no context scratch, so it can be captured (me_capture_begin)
+ * without a warm-up call.  me_partition_leaf_field* copy int16 vectors whatever
+ * their unit: they take &d_out->f unchanged and give the quarter-pel leaf field
+ * (block size B/2) that me_compensate_planes_qpel takes. */
+me_status me_partition_refine_qpel_device(me_ctx* ctx, const uint8_t* d_ref,
+                                          size_t ref_frame_stride, const uint8_t* d_cur,
+                                          size_t cur_frame_stride, int width, int height,
+                                          int stride, int block_size, me_cost cost,
+                                          uint32_t lambda, int n_frames, const int16_t* d_pred_q,
+                                          const me_part_fields* d_in,
+                                          const me_part_rd_fields* d_out, void* stream);
+
+/* The same on host planes of row pitch `stride` and host arrays, synchronous.
+ * A component beyond ME_QPEL_MAX_MV in any of the four input grids: ME_EINVAL. */
+me_status me_partition_refine_qpel(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int width,
+                                   int height, int stride, int block_size, me_cost cost,
+                                   uint32_t lambda, const int16_t* pred_q,
+                                   const me_part_fields* in, const me_part_rd_fields* out);
+
+/* me_partition_rd_search at SAD, the refinement above at `cost` and, if
+ * leaf_mv_q is not NULL, the leaf field ([nhy][nhx][2], quarter-pel units),
+ * back to back on the device with the same predictor and lambda: no field
+ * visits the host in between.  ME_COST_SAD, or ME_COST_SATD (the search then
+ * runs at SAD and the refinement at SATD); any other cost gets the status
+ * me_full_search_rd_qpel gives it.  One context device.  pred_q may be NULL. */
+me_status me_partition_search_qpel(me_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int width,
+                                   int height, int stride, int block_size, int search_range,
+                                   me_cost cost, uint32_t lambda, const int16_t* pred_q,
+                                   const me_part_rd_fields* out, int16_t* leaf_mv_q);
+
 /* ---- frame-pair streaming ---- */
 
 /* Pinned (page-locked) host memory.  Frames that live in it are DMAed

@@ -152,6 +152,14 @@ _SIGS = {
                                       [ctypes.c_uint32, ctypes.c_int] + [ctypes.c_void_p] * 3),
     "me_partition_rd_search": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] + [ctypes.c_int] * 6 +
                                [ctypes.c_uint32] + [ctypes.c_void_p] * 2),
+    # (in: ctypes.byref(engine.PartFields), out: ctypes.byref(engine.PartRdFields))
+    "me_partition_refine_qpel_device": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_size_t, _u8p,
+                                                       ctypes.c_size_t] + [ctypes.c_int] * 5 +
+                                        [ctypes.c_uint32, ctypes.c_int] + [ctypes.c_void_p] * 4),
+    "me_partition_refine_qpel": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] + [ctypes.c_int] * 5 +
+                                 [ctypes.c_uint32] + [ctypes.c_void_p] * 3),
+    "me_partition_search_qpel": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p] + [ctypes.c_int] * 6 +
+                                 [ctypes.c_uint32] + [ctypes.c_void_p] * 3),
     "me_mv_read_header": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
     "me_mv_read": (ctypes.c_int, [ctypes.c_char_p] + [ctypes.c_void_p] * 4),
 }

@@ -143,6 +143,30 @@ me_status partition_rd(int n_devs, const void* ref, const void* cur, int width, 
   return ME_OK;
 }
 
+me_status partition_qpel(int n_devs, const void* ref, const void* cur, int width, int height,
+                         int stride, int blk, int cost, uint32_t lambda, const me_part_fields* in,
+                         const me_part_rd_fields* out, int counts[4], char* err, size_t n) {
+  if (!ref || !cur || !in || !out) return fail(err, n, ME_EINVAL, "null plane or field pointer");
+  if (!in->mv_2nx2n || !in->mv_2nxn || !in->mv_nx2n || !in->mv_nxn)
+    return fail(err, n, ME_EINVAL, "null integer partition vector field");
+  if (!out->f.mv_2nx2n || !out->f.mv_2nxn || !out->f.mv_nx2n || !out->f.mv_nxn || !out->f.mode)
+    return fail(err, n, ME_EINVAL, "null partition vector field or mode array");
+  if (!valid_cost(cost)) return fail(err, n, ME_EINVAL, "cost %d", cost);
+  const char* why = "";
+  const me_status s = partition_check(width, height, stride, blk, 0, &why);
+  if (s != ME_OK)
+    return fail(err, n, s, "%s (%dx%d pitch %d, B %d)", why, width, height, stride, blk);
+  if (cost == ME_COST_SSIM)
+    return fail(err, n, ME_EUNSUPPORTED,
+                "partition-wise refinement has no SSIM cost (SAD, SSD or SATD)");
+  if (lambda > ME_PART_RD_MAX_LAMBDA)
+    return fail(err, n, ME_EINVAL, "lambda %u above ME_PART_RD_MAX_LAMBDA", lambda);
+  if (n_devs > 1) return one_device(n_devs, "partition-wise refinement", err, n);
+  if (me_partition_counts(width, height, blk, counts) != ME_OK)
+    return fail(err, n, ME_EINVAL, "frame %dx%d", width, height);
+  return ME_OK;
+}
+
 me_status partition_leaf(int n_devs, int width, int height, int blk, int n_frames,
                          const me_part_fields* in, const void* leaf, char* err, size_t n) {
   me_status s = frame_batch(n_frames, nullptr, 0, err, n);

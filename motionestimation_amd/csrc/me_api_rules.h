@@ -52,6 +52,11 @@ me_status partition(int n_devs, const void* ref, const void* cur, int width, int
 me_status partition_rd(int n_devs, const void* ref, const void* cur, int width, int height,
                        int stride, int blk, int range, int cost, uint32_t lambda,
                        const me_part_rd_fields* out, int counts[4], char* err, size_t n);
+// Partition-wise quarter-pel refinement of in's four integer grids into out
+// (B, plane size, cost, lambda, one device; no search range).
+me_status partition_qpel(int n_devs, const void* ref, const void* cur, int width, int height,
+                         int stride, int blk, int cost, uint32_t lambda, const me_part_fields* in,
+                         const me_part_rd_fields* out, int counts[4], char* err, size_t n);
 me_status partition_leaf(int n_devs, int width, int height, int blk, int n_frames,
                          const me_part_fields* in, const void* leaf, char* err, size_t n);
 // Rate-constrained search; rd_ctx: what its refinement shares with it.

@@ -1,6 +1,7 @@
 // me_api_stages.hip -- C ABI of libme_hip.so (include/me.h), the stages that
 // work on a searched field: compensation, quarter-pel refinement,
-// bi-prediction, partition search and the rate-constrained searches.
+// bi-prediction, partition search, the rate-constrained searches and the
+// partition-wise quarter-pel refinement.
 //
 // Every entry point is its argument rules (me_api_rules.cpp, in the order
 // written here), then for a host call upload_planes and a record layout, then
@@ -183,6 +184,28 @@ me_status search_and_refine(me_ctx* c, Dev& d, const uint8_t* ref, int width, in
   const FrameBatch b = packed(d, ref, width, height, blk);
   return enqueue(c, d, d.stream, "quarter-pel refinement",
                  [&](hipStream_t st) { return launch_qpel_refine(b, cost, mv, mv, bcost, st); });
+}
+
+// d.rec under layout_partition_rd as a struct of device pointers.
+me_part_rd_fields part_rd_records(Dev& d, const R::Layout& L) {
+  auto v = [&](int k) { return rec_at<int16_t>(d, L, R::PRD_MV + k); };
+  auto w = [&](int k) { return rec_at<uint32_t>(d, L, k); };
+  auto u = [&](int k) { return rec_at<uint8_t>(d, L, k); };
+  const int C = R::PRD_COST, Di = R::PRD_DIST, Bi = R::PRD_BITS;
+  return me_part_rd_fields{{v(0), v(1), v(2), v(3), w(C), w(C + 1), w(C + 2), w(C + 3),
+                            u(R::PRD_MODE), w(R::PRD_MODE_COST)},
+                           w(Di), w(Di + 1), w(Di + 2), w(Di + 3),
+                           u(Bi), u(Bi + 1), u(Bi + 2), u(Bi + 3)};
+}
+// The host arrays of out in layout_partition_rd's order (the predictors stay).
+void part_rd_host(const me_part_rd_fields* out, void* (&to)[19]) {
+  const me_part_fields& f = out->f;
+  void* const t[19] = {nullptr,         f.mv_2nx2n,      f.mv_2nxn,       f.mv_nx2n,
+                       f.mv_nxn,        f.cost_2nx2n,    f.cost_2nxn,     f.cost_nx2n,
+                       f.cost_nxn,      out->dist_2nx2n, out->dist_2nxn,  out->dist_nx2n,
+                       out->dist_nxn,   f.mode_cost,     out->bits_2nx2n, out->bits_2nxn,
+                       out->bits_nx2n,  out->bits_nxn,   f.mode};
+  for (int k = 0; k < 19; k++) to[k] = t[k];
 }
 
 }  // namespace
@@ -599,6 +622,94 @@ me_status me_partition_rd_search(me_ctx* c, const uint8_t* ref, const uint8_t* c
                         f.cost_nxn,      out->dist_2nx2n, out->dist_2nxn,  out->dist_nx2n,
                         out->dist_nxn,   f.mode_cost,     out->bits_2nx2n, out->bits_2nxn,
                         out->bits_nx2n,  out->bits_nxn,   f.mode};
+  return download_all(c, d, L, to, true);
+}
+
+// ---- partition-wise quarter-pel refinement (me_subpel.hip) ----
+
+me_status me_partition_refine_qpel_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
+                                          const uint8_t* d_cur, size_t cur_frame_stride, int width,
+                                          int height, int stride, int blk, me_cost cost,
+                                          uint32_t lambda, int n_frames, const int16_t* d_pred_q,
+                                          const me_part_fields* d_in,
+                                          const me_part_rd_fields* d_out, void* stream) {
+  if (!c) return ME_EINVAL;
+  TRY(R::frame_batch(n_frames, nullptr, 0, ERR(c)));
+  int n[4];
+  TRY(R::partition_qpel((int)c->devs.size(), d_ref, d_cur, width, height, stride, blk, cost,
+                        lambda, d_in, d_out, n, ERR(c)));
+  TRY(check_frames(c, n_frames, stride, height, ref_frame_stride, cur_frame_stride));
+  const FrameBatch b{d_ref, ref_frame_stride, d_cur, cur_frame_stride, width, height, stride, blk,
+                     n_frames};
+  return enqueue(c, c->devs[0], (hipStream_t)stream, "partition-wise refinement", [&](hipStream_t st) {
+    return launch_partition_qpel(b, cost, lambda, d_pred_q, *d_in, *d_out, st);
+  });
+}
+
+me_status me_partition_refine_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
+                                   int height, int stride, int blk, me_cost cost, uint32_t lambda,
+                                   const int16_t* pred_q, const me_part_fields* in,
+                                   const me_part_rd_fields* out) {
+  if (!c) return ME_EINVAL;
+  int n[4];
+  TRY(R::partition_qpel((int)c->devs.size(), ref, cur, width, height, stride, blk, cost, lambda,
+                        in, out, n, ERR(c)));
+  const int16_t* const grids[4] = {in->mv_2nx2n, in->mv_2nxn, in->mv_nx2n, in->mv_nxn};
+  for (int g = 0; g < 4; g++)
+    TRY(R::vectors(&grids[g], 1, (size_t)n[g], ME_QPEL_MAX_MV, "ME_QPEL_MAX_MV", ERR(c)));
+  const R::Layout L = R::layout_partition_rd(n);
+  Dev& d = c->devs[0];
+  TRY(upload_planes(c, d, {ref, cur}, width, height, stride, L.total));
+  int16_t* d_pred = pred_q ? rec_at<int16_t>(d, L, R::PRD_PRED) : nullptr;  // (null: zeros)
+  if (d_pred) TRY(upload(c, d, d_pred, pred_q, L.bytes[R::PRD_PRED]));
+  const me_part_rd_fields D = part_rd_records(d, L);
+  // the integer grids go where the refined ones come out: refined in place
+  int16_t* const dmv[4] = {D.f.mv_2nx2n, D.f.mv_2nxn, D.f.mv_nx2n, D.f.mv_nxn};
+  for (int g = 0; g < 4; g++) TRY(upload(c, d, dmv[g], grids[g], L.bytes[R::PRD_MV + g]));
+  const FrameBatch b = packed(d, d.ref, width, height, blk);
+  TRY(enqueue(c, d, d.stream, "partition-wise refinement", [&](hipStream_t st) {
+    return launch_partition_qpel(b, cost, lambda, d_pred, D.f, D, st);
+  }));
+  void* to[19];
+  part_rd_host(out, to);
+  return download_all(c, d, L, to, true);
+}
+
+me_status me_partition_search_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* cur, int width,
+                                   int height, int stride, int blk, int range, me_cost cost,
+                                   uint32_t lambda, const int16_t* pred_q,
+                                   const me_part_rd_fields* out, int16_t* leaf_mv_q) {
+  if (!c) return ME_EINVAL;
+  int n[4];
+  // (SATD: the search runs at SAD, the refinement at SATD)
+  TRY(R::partition_rd((int)c->devs.size(), ref, cur, width, height, stride, blk, range,
+                      R::search_cost(cost), lambda, out, n, ERR(c)));
+  const R::Layout L = R::layout_partition_rd(n);
+  const size_t leaf_bytes = 4 * (size_t)n[3];  // after the records (L.total is 8-aligned)
+  Dev& d = c->devs[0];
+  TRY(upload_planes(c, d, {ref, cur}, width, height, stride, L.total + leaf_bytes));
+  int16_t* d_pred = pred_q ? rec_at<int16_t>(d, L, R::PRD_PRED) : nullptr;  // (null: zeros)
+  if (d_pred) TRY(upload(c, d, d_pred, pred_q, L.bytes[R::PRD_PRED]));
+  const me_part_rd_fields D = part_rd_records(d, L);
+  int16_t* d_leaf = reinterpret_cast<int16_t*>(d.rec + L.total);
+  const FrameBatch b = packed(d, d.ref, width, height, blk);
+  const bool fast = dma_fast(me_partition_rd_kernel_variant(width, height, width, blk, range,
+                                                            lambda) == ME_PART_KERNEL_FAST, b);
+  TRY(enqueue(c, d, d.stream, "rate-constrained partition search", [&](hipStream_t st) {
+    return launch_partition_rd_search(b, range, lambda, fast, d_pred, D, st);
+  }));
+  // the searched vectors stay inside the window (|m| <= ME_PART_MAX_RANGE): refine in place
+  TRY(enqueue(c, d, d.stream, "partition-wise refinement", [&](hipStream_t st) {
+    return launch_partition_qpel(b, cost, lambda, d_pred, D.f, D, st);
+  }));
+  if (leaf_mv_q) {
+    TRY(enqueue(c, d, d.stream, "partition leaf field", [&](hipStream_t st) {
+      return launch_partition_leaf(width, height, blk, 1, D.f, d_leaf, st);
+    }));
+    TRY(download(c, d, leaf_mv_q, d_leaf, leaf_bytes));
+  }
+  void* to[19];
+  part_rd_host(out, to);
   return download_all(c, d, L, to, true);
 }
 

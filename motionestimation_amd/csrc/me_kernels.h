@@ -159,6 +159,14 @@ hipError_t launch_rd_search(const FrameBatch& b, int range, uint32_t lambda, boo
 hipError_t launch_partition_rd_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,
                                       const int16_t* pred, const me_part_rd_fields& out,
                                       hipStream_t stream);
+// Partition-wise quarter-pel refinement (me_subpel.hip): the four integer grids
+// of `in` (the rest of it is not read) refined partition by partition on
+// cost + lambda * bits(q - pred) and the mode decided on the refined J.  Frames,
+// records and pred laid out as for launch_partition_rd_search; out's grids may
+// be in's; blk in {8, 16, 32}.  No context scratch.
+hipError_t launch_partition_qpel(const FrameBatch& b, int cost, uint32_t lambda,
+                                 const int16_t* pred, const me_part_fields& in,
+                                 const me_part_rd_fields& out, hipStream_t stream);
 // launch_compensate with quarter-pel vectors and edge-replicated samples.
 hipError_t launch_qpel_compensate(const uint8_t* ref, const uint8_t* cur, int width, int height,
                                   int blk, const int16_t* mvq, uint8_t* out5, int write_planes,

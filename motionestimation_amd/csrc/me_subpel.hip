@@ -1,8 +1,10 @@
 // me_subpel.hip -- quarter-pel refinement of an integer MV field, sub-pel
-// motion compensation, and the bi-predictive mode decision over two
-// quarter-pel fields with its compensation (include/me.h "quarter-pel" and
-// "bi-predictive"; DESIGN.md has the definitions and the LDS layouts).  No
-// reference counterpart: the reference stops at integer vectors.
+// motion compensation, the bi-predictive mode decision over two quarter-pel
+// fields with its compensation, and the partition-wise refinement of a
+// partition search's four grids with its mode decision (include/me.h
+// "quarter-pel", "bi-predictive" and "partition-wise quarter-pel refinement";
+// DESIGN.md has the definitions and the LDS layouts).  No reference
+// counterpart: the reference stops at integer vectors.
 //
 // Sample definition (H.264 luma, exact integers): reference samples are edge
 // replicated, half samples are the 6-tap (1,-5,20,20,-5,1) filter rounded
@@ -32,6 +34,7 @@
 
 #include "me.h"
 #include "me_kernels.h"
+#include "me_partition_lane.h"
 #include "me_rd.h"
 
 namespace me {
@@ -783,6 +786,313 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_bipred_compensate_kernel(
   }
 }
 
+// ---- partition-wise quarter-pel refinement (include/me.h "partition-wise
+// quarter-pel refinement"; DESIGN.md has the layout and the counts) ----
+//
+// One workgroup per macroblock refines its nine partitions (P_FULL .. P_BR of
+// me_partition_lane.h's order: the macroblock, top, bottom, left, right, and
+// the quarters TL, TR, BL, BR).  The lanes keep qpel_pixels' layout of the
+// whole macroblock, one 4-pixel group each (GPL = 1 for B in {8, 16, 32}); a
+// group lies in exactly one quarter, so a candidate is costed once per lane
+// and reduced per quarter: every partition's cost is a sum of quarter sums
+// (SATD too: its tiles are anchored at multiples of 4 and the quarters at
+// multiples of h >= 4).
+//
+// Partitions are grouped by integer vector.  The window is staged and the half
+// grid built once per distinct vector, over the bounding rectangle of the
+// partitions that hold it; stage 1's nine candidates are the same positions
+// for all of them.  Stage 2 then runs once per distinct stage-1 centre within
+// the group, on the same half grid.  Everything a decision depends on is
+// uniform over the workgroup, so the loops and branches are too.
+// Per partition: its quarters (bit k: TL, TR, BL, BR), its grid, and its cell's
+// offset in the macroblock.
+__host__ __device__ constexpr int pq_quads(int p) {
+  return (int)(0x8421A5C3Full >> (4 * p)) & 15;  // 15, 3, 12, 5, 10, 1, 2, 4, 8
+}
+__host__ __device__ constexpr int pq_grid(int p) { return p == 0 ? 0 : p < 3 ? 1 : p < 5 ? 2 : 3; }
+__host__ __device__ constexpr int pq_i(int p) { return p == P_RIGHT || p == P_TR || p == P_BR; }
+__host__ __device__ constexpr int pq_j(int p) { return p == P_BOT || p == P_BL || p == P_BR; }
+
+struct PartQpelIO {
+  const int16_t* in[4];  // integer grids
+  int16_t* mv[4];
+  uint32_t* cost[4];  // each may be null
+  uint32_t* dist[4];
+  uint8_t* bits[4];
+  uint8_t* mode;
+  uint32_t* mode_cost;  // may be null
+  const int16_t* pred;  // null: all zero
+  int nx[4], ny[4];     // the four grids
+  uint32_t lambda;
+};
+
+template <int TB>
+struct PartQpelLds : QpelLds<TB> {
+  uint32_t qred[QpelGeom<TB>::NW * 9 * 2];  // per wave and candidate: left, right
+};
+
+// Sums over each row of 16 lanes, in the row's lane 15.
+__device__ __forceinline__ int row_sum(uint32_t v) {
+  int x = (int)v;
+  x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false);  // row_shr:1
+  x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, false);  // row_shr:2
+  x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, false);  // row_shr:4
+  x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, false);  // row_shr:8
+  return x;
+}
+
+// A partition's cost from the quarter sums (quads: its quarters).
+__device__ __forceinline__ uint32_t part_sum(const uint32_t (&q)[4], int quads) {
+  uint32_t c = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) c += quads >> k & 1 ? q[k] : 0;
+  return c;
+}
+
+// v[n] summed over the lanes of each quarter (qi: the lane's), and from the
+// quarter sums c[n]: the cost of the partition whose quarters are `quads` (the
+// lane's own partition: any lane may ask for another one).  n = 4 only when
+// CENTRE.
+template <int TB, bool CENTRE>
+__device__ __forceinline__ void part_sums(PartQpelLds<TB>& s, const uint32_t (&v)[9], int qi,
+                                          int quads, uint32_t (&c)[9]) {
+  using G = QpelGeom<TB>;
+  if constexpr (TB == 16) {
+    // lane = 4 py + px0 / 4: a row of 16 lanes is 4 pixel rows, rows 0 and 1 the top
+#pragma unroll
+    for (int n = 0; n < 9; n++) {
+      if (n == 4 && !CENTRE) continue;
+      const int l = row_sum(qi & 1 ? 0 : v[n]), r = row_sum(qi & 1 ? v[n] : 0);
+      const uint32_t q[4] = {
+          (uint32_t)(__builtin_amdgcn_readlane(l, 15) + __builtin_amdgcn_readlane(l, 31)),
+          (uint32_t)(__builtin_amdgcn_readlane(r, 15) + __builtin_amdgcn_readlane(r, 31)),
+          (uint32_t)(__builtin_amdgcn_readlane(l, 47) + __builtin_amdgcn_readlane(l, 63)),
+          (uint32_t)(__builtin_amdgcn_readlane(r, 47) + __builtin_amdgcn_readlane(r, 63))};
+      c[n] = part_sum(q, quads);
+    }
+  } else if constexpr (G::NW == 4) {
+    // thread = 8 py + px0 / 4: waves 0 and 1 are the top half
+    uint32_t l[9], r[9];
+#pragma unroll
+    for (int n = 0; n < 9; n++) {
+      if (n == 4 && !CENTRE) continue;
+      l[n] = wave_sum(qi & 1 ? 0 : v[n]);
+      r[n] = wave_sum(qi & 1 ? v[n] : 0);
+    }
+    __syncthreads();  // the previous sums have been read
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+      for (int n = 0; n < 9; n++) {
+        if (n == 4 && !CENTRE) continue;
+        s.qred[((threadIdx.x >> 6) * 9 + n) * 2] = l[n];
+        s.qred[((threadIdx.x >> 6) * 9 + n) * 2 + 1] = r[n];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < 9; n++) {
+      if (n == 4 && !CENTRE) continue;
+      uint32_t q[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int w = k & 2;  // first wave of the half
+        q[k] = s.qred[(w * 9 + n) * 2 + (k & 1)] + s.qred[((w + 1) * 9 + n) * 2 + (k & 1)];
+      }
+      c[n] = part_sum(q, quads);
+    }
+  } else {
+    static_assert(G::NW == 1, "one wave");
+#pragma unroll
+    for (int n = 0; n < 9; n++) {
+      if (n == 4 && !CENTRE) continue;
+      uint32_t q[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) q[k] = wave_sum(qi == k ? v[n] : 0);
+      c[n] = part_sum(q, quads);
+    }
+  }
+}
+
+// out[n]: the cost of the partition `quads` at the candidates centre + step *
+// (dx, dy) in raster order n (n = 4, the centre, only when CENTRE).  The lane's
+// group is at (px0, py) of the staged rectangle: cur bytes c, mask m (0: a lane
+// outside the rectangle), cc the lane's sum c^2 (SSD).
+template <int TB, int COST, bool CENTRE>
+__device__ __forceinline__ void part_qpel_costs(PartQpelLds<TB>& s, int px0, int py, uint32_t c,
+                                                uint32_t m, uint32_t cc, int qi, int quads,
+                                                int cx, int cy, int step, uint32_t (&out)[9]) {
+  uint32_t v[9];
+#pragma unroll
+  for (int n = 0; n < 9; n++) {
+    v[n] = 0;
+    if (n == 4 && !CENTRE) continue;
+    const QpelTaps t = qpel_taps(cx + step * (n % 3 - 1), cy + step * (n / 3 - 1));
+    uint32_t pp = 0, pc = 0;
+    cost4<TB, COST>(qpel_pred4<TB>(s.hg, px0, py, t) & m, c, pp, pc);
+    v[n] = COST == ME_COST_SSD ? pp + cc - 2 * pc : pp;
+  }
+  part_sums<TB, CENTRE>(s, v, qi, quads, out);
+}
+
+// Lane p < 9 of every wave keeps partition p's record (every wave the same
+// nine: what a decision reads is the same in all of them), so the nine
+// decisions of a candidate are one compare, and what the group loops read of
+// them (a vector, a centre, who shares it) is a v_readlane or a ballot.  The
+// grids may be refined in place (io.mv[g] == io.in[g]): a workgroup reads its
+// macroblock's nine vectors before its first barrier and writes its records
+// after its last, and every cell belongs to exactly one macroblock.
+template <int TB, int COST>
+__global__ __launch_bounds__(QpelGeom<TB>::NT) void me_partition_qpel_kernel(
+    const uint8_t* __restrict__ ref, size_t ref_frame_stride, const uint8_t* __restrict__ cur,
+    size_t cur_frame_stride, int width, int height, int stride, PartQpelIO io) {
+  using G = QpelGeom<TB>;
+  static_assert(G::GPL == 1, "one 4-pixel group per lane");
+  constexpr int h = TB / 2;
+  __shared__ PartQpelLds<TB> s;
+  const int nbx = io.nx[0];
+  const int bx = (int)blockIdx.x % nbx, by = (int)blockIdx.x / nbx, f = blockIdx.y;
+  const int x0 = bx * TB, y0 = by * TB;
+  const int bw = min(TB, width - x0), bh = min(TB, height - y0);
+  const size_t mb = (size_t)f * nbx * io.ny[0] + (size_t)by * nbx + bx;
+  const int px = io.pred ? io.pred[2 * mb] : 0, py = io.pred ? io.pred[2 * mb + 1] : 0;
+  ref += (size_t)f * ref_frame_stride;
+  cur += (size_t)f * cur_frame_stride;
+
+  // the lane's partition: it exists iff its cell is inside its grid
+  const int lane = threadIdx.x & 63, pl = min(lane, P_N - 1);
+  const int pg = pq_grid(pl), quads = pq_quads(pl);
+  // (its grid's arrays are picked here, into the lane's registers: the nine
+  // records leave in one store each, and the loops below keep no pointer table)
+  int gnx = 0, gny = 0;
+  const int16_t* gin = nullptr;
+  int16_t* omv = nullptr;
+  uint32_t *ocost = nullptr, *odist = nullptr;
+  uint8_t* obits = nullptr;
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    if (g == pg) {
+      gnx = io.nx[g], gny = io.ny[g], gin = io.in[g];
+      omv = io.mv[g], ocost = io.cost[g], odist = io.dist[g], obits = io.bits[g];
+    }
+  }
+  const int cxp = (pg >= 2 ? 2 : 1) * bx + pq_i(pl), cyp = (pg & 1 ? 2 : 1) * by + pq_j(pl);
+  const bool exists = lane < P_N && cxp < gnx && cyp < gny;
+  const size_t at = (size_t)f * gnx * gny + (size_t)cyp * gnx + cxp;
+  const int vx = exists ? gin[2 * at] : 0, vy = exists ? gin[2 * at + 1] : 0;
+  const uint32_t exist = (uint32_t)__ballot(exists);
+
+  QpelPix<TB> P;
+  qpel_pixels<TB>(P, cur + (size_t)y0 * stride + x0, stride, bw, bh);
+  // the lane's quarter, from its nominal position: a lane below a clipped
+  // macroblock's last row holds no pixels (P puts it at the origin) but, under
+  // SATD, a share of the partial tile above it
+  const int qi = ((int)threadIdx.x / G::GW >= h ? 2 : 0) + ((int)threadIdx.x % G::GW * 4 >= h ? 1 : 0);
+  const uint32_t cc_all =
+      COST == ME_COST_SSD ? __builtin_amdgcn_udot4(P.cur[0], P.cur[0], 0u, false) : 0u;
+
+  uint32_t best = 0, dist = 0;
+  int c1 = 4;          // raster index of the stage-1 winner (4: the centre)
+  int fx = 0, fy = 0;  // quarter offset of the best candidate from 4 * m
+
+#pragma unroll 1
+  for (int g = 0; g < P_N; g++) {
+    if (!(exist >> g & 1)) continue;
+    // the partitions that hold partition g's vector; g leads them if it is the first
+    const int gvx = __builtin_amdgcn_readlane(vx, g), gvy = __builtin_amdgcn_readlane(vy, g);
+    const uint32_t members = (uint32_t)__ballot(exists && vx == gvx && vy == gvy);
+    if (members & ((1u << g) - 1)) continue;
+    const bool member = members >> pl & 1 && lane < P_N;
+
+    // their bounding rectangle, clipped like the macroblock (the partitions
+    // that contain the quarters TL, TR, BL, BR: 0x2B, 0x53, 0x8D, 0x115)
+    const bool left = members & 0xAFu, top = members & 0x7Bu;       // TL or BL; TL or TR
+    const bool right = members & 0x157u, bottom = members & 0x19Du;  // TR or BR; BL or BR
+    const int rx = left ? 0 : h, ry = top ? 0 : h;
+    const int rw = min(right ? TB : h, bw) - rx, rh = min(bottom ? TB : h, bh) - ry;
+    const bool in = P.px0[0] >= rx && P.px0[0] < rx + rw && P.py[0] >= ry && P.py[0] < ry + rh;
+    const int lx = in ? P.px0[0] - rx : 0, ly = in ? P.py[0] - ry : 0;
+    const uint32_t lm = in ? P.mask[0] : 0, lc = in ? P.cur[0] : 0, lcc = in ? cc_all : 0;
+    qpel_stage<TB>(s, ref, width, height, stride, x0 + rx + gvx, y0 + ry + gvy, rw, rh);
+    qpel_half_grid<TB>(s, rw, rh);
+
+    // the centre relative to the predictor, in quarter units
+    const int ex = 4 * gvx - px, ey = 4 * gvy - py;
+    uint32_t c9[9];
+    {
+      uint32_t rbx[3], rby[3];
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        rbx[i] = io.lambda * (uint32_t)rd_bits(ex + 2 * (i - 1));
+        rby[i] = io.lambda * (uint32_t)rd_bits(ey + 2 * (i - 1));
+      }
+      part_qpel_costs<TB, COST, true>(s, lx, ly, lc, lm, lcc, qi, quads, 0, 0, 2, c9);
+      uint32_t d = c9[4], b = d + rbx[1] + rby[1];
+      int w = 4;
+#pragma unroll
+      for (int n = 0; n < 9; n++) {
+        if (n == 4) continue;
+        const uint32_t dn = c9[n], j = dn + rbx[n % 3] + rby[n / 3];
+        if (j < b) b = j, d = dn, w = n;
+      }
+      if (member) {
+        best = b, dist = d, c1 = w;
+        fx = 2 * (w % 3 - 1), fy = 2 * (w / 3 - 1);
+      }
+    }
+
+    // stage 2 on the same half grid, once per distinct carried centre
+#pragma unroll 1
+    for (int l = g; l < P_N; l++) {
+      if (!(members >> l & 1)) continue;
+      const int lc1 = __builtin_amdgcn_readlane(c1, l);
+      const uint32_t same = (uint32_t)__ballot(member && c1 == lc1);
+      if (same & ((1u << l) - 1)) continue;
+      const int cx = 2 * (lc1 % 3 - 1), cy = 2 * (lc1 / 3 - 1);
+      uint32_t rbx[3], rby[3];
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        rbx[i] = io.lambda * (uint32_t)rd_bits(ex + cx + i - 1);
+        rby[i] = io.lambda * (uint32_t)rd_bits(ey + cy + i - 1);
+      }
+      part_qpel_costs<TB, COST, false>(s, lx, ly, lc, lm, lcc, qi, quads, cx, cy, 1, c9);
+      const bool mine = member && c1 == lc1;
+#pragma unroll
+      for (int n = 0; n < 9; n++) {
+        if (n == 4) continue;
+        const uint32_t dn = c9[n], j = dn + rbx[n % 3] + rby[n / 3];
+        if (mine && j < best) best = j, dist = dn, fx = cx + n % 3 - 1, fy = cy + n / 3 - 1;
+      }
+    }
+  }
+
+  if (threadIdx.x < P_N) {
+    const int qx = 4 * vx + fx, qy = 4 * vy + fy;
+    if (exists) {
+      omv[2 * at] = (int16_t)qx;
+      omv[2 * at + 1] = (int16_t)qy;
+      if (ocost) ocost[at] = best;
+      if (odist) odist[at] = dist;
+      if (obits) obits[at] = (uint8_t)(rd_bits(qx - px) + rd_bits(qy - py));
+    }
+    // a missing partition's best is 0: it adds nothing
+    uint32_t jp[P_N];
+#pragma unroll
+    for (int p = 0; p < P_N; p++) jp[p] = (uint32_t)__builtin_amdgcn_readlane((int)best, p);
+    const uint32_t j0 = jp[P_FULL] + io.lambda, j1 = jp[P_TOP] + jp[P_BOT] + 3 * io.lambda;
+    const uint32_t j2 = jp[P_LEFT] + jp[P_RIGHT] + 3 * io.lambda;
+    const uint32_t j3 = jp[P_TL] + jp[P_TR] + jp[P_BL] + jp[P_BR] + 5 * io.lambda;
+    uint32_t bj = j0;
+    int mode = ME_PART_2Nx2N;
+    if (j1 < bj) bj = j1, mode = ME_PART_2NxN;
+    if (j2 < bj) bj = j2, mode = ME_PART_Nx2N;
+    if (j3 < bj) bj = j3, mode = ME_PART_NxN;
+    if (threadIdx.x == 0) {
+      io.mode[mb] = (uint8_t)mode;
+      if (io.mode_cost) io.mode_cost[mb] = bj;
+    }
+  }
+}
+
 int tile_of(int blk) { return blk <= 4 ? 4 : blk <= 8 ? 8 : blk <= 16 ? 16 : blk <= 32 ? 32 : 64; }
 
 // cost: ME_COST_SSD, ME_COST_SAD or ME_COST_SATD (the callers reject the rest).
@@ -912,6 +1222,50 @@ hipError_t launch_bipred(const FrameBatch& b, const uint8_t* ref1, size_t ref1_f
   }
 #undef ME_BIPRED
 #undef ME_BIPRED_K
+  return hipGetLastError();
+}
+
+hipError_t launch_partition_qpel(const FrameBatch& b, int cost, uint32_t lambda,
+                                 const int16_t* pred, const me_part_fields& in,
+                                 const me_part_rd_fields& out, hipStream_t stream) {
+  const int h = b.blk / 2;
+  const int nbx = (b.width + b.blk - 1) / b.blk, nby = (b.height + b.blk - 1) / b.blk;
+  const int nhx = (b.width + h - 1) / h, nhy = (b.height + h - 1) / h;
+  const me_part_fields& f = out.f;
+  const PartQpelIO io{{in.mv_2nx2n, in.mv_2nxn, in.mv_nx2n, in.mv_nxn},
+                      {f.mv_2nx2n, f.mv_2nxn, f.mv_nx2n, f.mv_nxn},
+                      {f.cost_2nx2n, f.cost_2nxn, f.cost_nx2n, f.cost_nxn},
+                      {out.dist_2nx2n, out.dist_2nxn, out.dist_nx2n, out.dist_nxn},
+                      {out.bits_2nx2n, out.bits_2nxn, out.bits_nx2n, out.bits_nxn},
+                      f.mode,
+                      f.mode_cost,
+                      pred,
+                      {nbx, nbx, nhx, nhx},
+                      {nby, nhy, nby, nhy},
+                      lambda};
+  const dim3 grid((unsigned)(nbx * nby), (unsigned)b.n_frames);
+#define ME_PART_QPEL_K(TB, COST)                                                              \
+  hipLaunchKernelGGL((me_partition_qpel_kernel<TB, COST>), grid, dim3(QpelGeom<TB>::NT), 0,   \
+                     stream, b.ref, b.ref_frame_stride, b.cur, b.cur_frame_stride, b.width,   \
+                     b.height, b.stride, io)
+#define ME_PART_QPEL(TB)               \
+  case TB:                             \
+    if (cost == ME_COST_SSD)           \
+      ME_PART_QPEL_K(TB, ME_COST_SSD); \
+    else if (cost == ME_COST_SATD)     \
+      ME_PART_QPEL_K(TB, ME_COST_SATD);\
+    else                               \
+      ME_PART_QPEL_K(TB, ME_COST_SAD); \
+    break
+  switch (b.blk) {  // (the entry points admit 8, 16 and 32 only)
+    ME_PART_QPEL(8);
+    ME_PART_QPEL(16);
+    ME_PART_QPEL(32);
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef ME_PART_QPEL
+#undef ME_PART_QPEL_K
   return hipGetLastError();
 }
 

@@ -539,6 +539,57 @@ class Engine:
             _ptr(pred) if pred is not None else None, ctypes.byref(st)), self._h)
         return out
 
+    # ---- partition-wise quarter-pel refinement (include/me.h) ----
+    def partition_refine_qpel(self, ref, cur, blk: int, fields, lam: int = 0, pred=None,
+                              cost="sad", width=None) -> "PartitionRdFields":
+        """The four integer grids of fields (a PartitionFields of numpy arrays;
+        only mv is read) refined to quarter-pel partition by partition on
+        cost + lam * bits(q - pred), and the mode decided again on the refined J
+        (me_partition_refine_qpel); pred int16 [macroblocks, 2] in quarter-pel
+        units or None (all zero).  Returns PartitionRdFields of numpy arrays
+        with mv in quarter-pel units."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        cur = np.ascontiguousarray(cur, dtype=np.uint8)
+        if ref.ndim != 2 or ref.shape != cur.shape:
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {ref.shape} vs {cur.shape}")
+        h, pitch = ref.shape
+        w = width or pitch
+        out = PartitionRdFields.host(w, h, blk)
+        mv = [np.ascontiguousarray(a, np.int16) for a in fields.mv]
+        for a, o in zip(mv, out.mv):
+            if a.size != o.size:
+                raise MEError(_lib.ME_EINVAL, f"field of {a.size // 2} records for {o.size // 2} cells")
+        pred = self._pred(pred, out.mode.size)
+        st_in = PartitionFields(mv, None, out.mode, None).struct()
+        st = out.rd_struct()
+        check(_lib.lib().me_partition_refine_qpel(
+            self._h, _ptr(ref), _ptr(cur), w, h, pitch, blk, cost_code(cost), lam,
+            _ptr(pred) if pred is not None else None, ctypes.byref(st_in), ctypes.byref(st)),
+            self._h)
+        return out
+
+    def partition_search_qpel(self, ref, cur, blk: int, span: int, lam: int = 0, pred=None,
+                              cost="sad", width=None, leaf=True):
+        """partition_rd_search at SAD, partition_refine_qpel at cost ("sad" or
+        "satd") and, if leaf, the leaf field, back to back on the device
+        (me_partition_search_qpel).  Returns (PartitionRdFields, leaf int16
+        [nhx * nhy, 2] in quarter-pel units at block size blk / 2, or None)."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        cur = np.ascontiguousarray(cur, dtype=np.uint8)
+        if ref.ndim != 2 or ref.shape != cur.shape:
+            raise MEError(_lib.ME_EINVAL, f"plane shapes {ref.shape} vs {cur.shape}")
+        h, pitch = ref.shape
+        w = width or pitch
+        out = PartitionRdFields.host(w, h, blk)
+        pred = self._pred(pred, out.mode.size)
+        leaf_mv = np.zeros((out.mv[3].shape[0], 2), np.int16) if leaf else None
+        st = out.rd_struct()
+        check(_lib.lib().me_partition_search_qpel(
+            self._h, _ptr(ref), _ptr(cur), w, h, pitch, blk, span, cost_code(cost), lam,
+            _ptr(pred) if pred is not None else None, ctypes.byref(st),
+            _ptr(leaf_mv) if leaf else None), self._h)
+        return out, leaf_mv
+
     def refine_qpel_rd(self, ref, cur, blk: int, mv, lam: int = 0, pred=None, cost="ssd",
                        stride=None):
         """refine_qpel on cost + lam * bits(q - pred) (me_refine_qpel_rd).
@@ -877,6 +928,35 @@ class Engine:
             if s:
                 check(s, ctx)
         run.fields = st  # keep the pointer struct alive with the callable
+        return run
+
+    def partition_refine_qpel_device(self, ref_t, cur_t, blk: int, cost, lam: int, fields_in,
+                                     fields_out, pred_t=None, stream=None, width=None,
+                                     height=None):
+        """Enqueue the partition-wise quarter-pel refinement of resident frames
+        (me_partition_refine_qpel_device): fields_in a PartitionFields of torch
+        tensors whose four integer mv grids are read, fields_out a
+        PartitionRdFields of torch tensors (it may share fields_in's mv tensors:
+        in place), pred_t int16 [F * macroblocks, 2] or None (all zero)."""
+        self.prepared_partition_refine_qpel(ref_t, cur_t, blk, cost, lam, fields_in, fields_out,
+                                            pred_t, stream, width, height)()
+
+    def prepared_partition_refine_qpel(self, ref_t, cur_t, blk, cost, lam, fields_in, fields_out,
+                                       pred_t=None, stream=None, width=None, height=None):
+        """Zero-argument callable enqueueing partition_refine_qpel_device(...) with these buffers."""
+        frames, rfs, cfs, w, h, pitch = self._plane_args(ref_t, cur_t, width, height)
+        st_in, st = fields_in.struct(), fields_out.rd_struct()
+        fn, ctx = _lib.lib().me_partition_refine_qpel_device, self._h
+        args = (ctx, ref_t.data_ptr(), rfs, cur_t.data_ptr(), cfs, w, h, pitch, blk,
+                cost_code(cost), lam, frames, pred_t.data_ptr() if pred_t is not None else None,
+                ctypes.byref(st_in), ctypes.byref(st),
+                stream if stream is not None else _current_stream())
+
+        def run():
+            s = fn(*args)
+            if s:
+                check(s, ctx)
+        run.fields = (st_in, st)  # keep the pointer structs alive with the callable
         return run
 
     def refine_qpel_rd_device(self, ref_t, cur_t, blk: int, cost, lam: int, mv_t, q_t=None,
