@@ -98,9 +98,14 @@ struct QsadGeom {
   int prune;         // 1: on; 2: verify (every lane-task runs, a wrongly dead one is reported)
   int prune_bypass;  // 1: after a run of items the bound could not thin, skip it and re-probe
   int prune_stats;   // 1: live / total lane-tasks and bypassed items counted in sched[SCHED_PRUNE..]
-  int prune_slots;   // ring slots when pruning (each slot carries FLOW_PRUNE_BYTES of bound scratch)
-  int prune_lds;     // dynamic LDS bytes of the pruning launch
+  int prune_slots;   // ring slots when pruning without box-sum planes (each slot carries FLOW_PRUNE_BYTES of bound scratch)
+  int prune_lds;     // dynamic LDS bytes of that launch
   int prune_split;   // 1: a pruned item's short wave-task is split by dy rows (flow_split_* below)
+  // The pruning launch WITH box-sum planes (FlowJobs::planes): its bound reads
+  // the planes from global memory, a slot carries FLOW_SLIM_BYTES of scratch
+  // (0 slots: the shape's plane loads could straddle a phase row, no such launch).
+  int slim_slots;    // ring slots
+  int slim_lds;      // dynamic LDS bytes
 };
 
 // ---- row split of a pruned item's partial wave-task (me_flow_kernel) ----
@@ -133,16 +138,31 @@ static_assert(flow_split_fits(1) && flow_split_fits(2) && flow_split_fits(4), "6
 // planes of 77 rows x 32 box-sum bytes (the live list overlays them once the
 // bound is done), minlb[5][4][16] u32 and the cur blocks' 4 x 16 box-sum bytes.
 // Plane k, row r, byte i holds q of window position (r, 4 i + k), q = the 4x4
-// box sum >> 4.  The planes are filled one of two ways: by the staging wave's
-// LDS DMA from the job's box-sum planes in the context scratch (below; the
-// prepass me_box_planes_kernel wrote them once per reference plane), or, where
-// the launch has no such planes, by step 1 of flow_bound from the staged window.
+// box sum >> 4.  This is the layout of a launch WITHOUT box-sum planes in the
+// context scratch: step 1 of flow_bound fills the slot's planes from the staged
+// window.  A launch with them (the prepass me_box_planes_kernel wrote them once
+// per reference plane) keeps no planes in the slot: FLOW_SLIM_* below.
 constexpr int FLOW_PRUNE_QROWS = 77;
 constexpr int FLOW_PRUNE_PLANE = FLOW_PRUNE_QROWS * 32;
 constexpr int FLOW_PRUNE_MINLB = 4 * FLOW_PRUNE_PLANE;
 constexpr int FLOW_PRUNE_QCUR = FLOW_PRUNE_MINLB + 320 * 4;
 constexpr int FLOW_PRUNE_BYTES = FLOW_PRUNE_QCUR + 64;
 constexpr int FLOW_CTL_BYTES = 256;  // the pruning launch's control block (FlowCtl)
+// The slim bound scratch of a launch with box-sum planes: the bound's step 2
+// loads its plane rows from the job's planes in global memory into registers
+// (flow_plane_byte below), so the slot keeps only what outlives the bound or
+// is shared between its lanes: the live list (320 u16, verify: 320 flags at
+// FLOW_PRUNE_DEAD and U_b[4] at FLOW_PRUNE_UB, the offsets both layouts use),
+// minlb and the cur blocks' box sums.
+constexpr int FLOW_PRUNE_DEAD = 640;
+constexpr int FLOW_PRUNE_UB = 960;
+constexpr int FLOW_SLIM_MINLB = 1024;
+constexpr int FLOW_SLIM_QCUR = FLOW_SLIM_MINLB + 320 * 4;
+constexpr int FLOW_SLIM_BYTES = FLOW_SLIM_QCUR + 64;
+static_assert(FLOW_PRUNE_UB + 16 <= FLOW_SLIM_MINLB && FLOW_PRUNE_UB + 16 <= FLOW_PRUNE_MINLB,
+              "list, verify flags and U_b lie in front of minlb in both layouts");
+static_assert(FLOW_SLIM_BYTES == 2368 && FLOW_SLIM_BYTES % 16 == 0 && FLOW_PRUNE_BYTES % 16 == 0,
+              "slots stay 16-byte aligned");
 
 // A search job: block rows [r0, r1) of one frame (or row stripe), its planes
 // (ref / cur hold frame rows from ref_row0 / cur_row0, as in SearchArgs) and
@@ -228,7 +248,6 @@ ME_HOST_DEVICE inline int flow_job_find(const FlowJobs& jb, int tile) {
   }
   return lo;
 }
-#undef ME_HOST_DEVICE
 
 // ---- box-sum planes of the pruning flow plan (S = 32, 4-block tiles) ----
 // Per job, per resident ref row y (relative to ref_row0), four x-phase rows of
@@ -245,6 +264,32 @@ inline int flow_plane_rows(const SearchJob& J, int blk, int range, int height) {
 }
 inline size_t flow_plane_job_bytes(int width, int rows) {  // a multiple of 64
   return (size_t)rows * 4 * (size_t)flow_plane_pitch(width);
+}
+// Byte offset in a job's planes of x phase k, byte `byte` of the 32 an item's
+// window row yp (0 .. 76) has there: the item's window starts rel = prow0 -
+// ref_row0 rows into the job's resident rows, at x = X0 (= 64 c - 32 for tile
+// column c).  Unsigned arithmetic: a row above the resident ones wraps past
+// 2^31, a row below them lies past the job's bytes, and the buffer range check
+// reads either as 0 (the bytes the slot's LDS DMA of the planes brought).  The
+// bound's step 2 reads 8 bytes at byte = 4 b + 4 m of phase k (block b, dx
+// groups 4m .. 4m + 3), its fold column 4 bytes at byte = 4 b + 16 of phase 0.
+// The offset is the sum (mod 2^32) of a part the wave shares and the lane's;
+// the kernel forms the two apart and steps the row part by 4 * pitch a row.
+ME_HOST_DEVICE inline uint32_t flow_plane_row_byte(int pitch, int rel, int X0, int yp) {
+  return (uint32_t)(4 * (rel + yp)) * (uint32_t)pitch + (uint32_t)((X0 + 32) >> 2);
+}
+ME_HOST_DEVICE inline uint32_t flow_plane_lane_byte(int pitch, int k, int byte) {
+  return (uint32_t)k * (uint32_t)pitch + (uint32_t)byte;
+}
+ME_HOST_DEVICE inline uint32_t flow_plane_byte(int pitch, int rel, int X0, int yp, int k, int byte) {
+  return flow_plane_row_byte(pitch, rel, X0, yp) + flow_plane_lane_byte(pitch, k, byte);
+}
+#undef ME_HOST_DEVICE
+// No such load straddles the end of a phase row, so none straddles the end of
+// the job's bytes (a whole number of phase rows; the loads are 4-byte aligned,
+// the pitch a multiple of 16): the last tile column's 32 bytes end inside the pitch.
+inline bool flow_plane_loads_fit(int width, int wg_per_row) {
+  return wg_per_row >= 1 && 16 * (wg_per_row - 1) + 32 <= flow_plane_pitch(width);
 }
 
 // ---- the VALU kernels' planners (me_valu_plan.cpp: host-only, pure) ----

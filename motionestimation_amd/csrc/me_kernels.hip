@@ -963,8 +963,8 @@ struct FlowCtl {
   uint32_t stats[4];   // tuning build: live, all lane-tasks, bypassed items, items (flushed at the end)
   uint32_t split[3];   // tuning build: executed wave-tasks run with 1, 2, 4 lanes per list entry
 };
-// PF_PLANES: the launch has box-sum planes (FlowJobs::planes): the staging wave
-// DMAs an item's four planes with its window, and flow_bound skips its step 1.
+// PF_PLANES: the launch has box-sum planes (FlowJobs::planes): flow_bound skips
+// its step 1 and loads the plane rows of step 2 from them (the slim scratch).
 // PF_SPLIT: a pruned item's wave-task of <= 32 list entries is split by rows
 // (flow_split_task below).
 enum { PF_ON = 1, PF_VERIFY = 2, PF_BYPASS = 4, PF_STATS = 8, PF_PLANES = 16, PF_SPLIT = 32 };
@@ -984,19 +984,12 @@ __device__ __forceinline__ Item flow_item(const SearchArgs& p, const QsadGeom& g
 }
 
 // Single-wave LDS DMA of one flow item (the aligned path): tile rows and cur
-// blocks, from its job's planes.  PL (the pruning instance) and PF_PLANES set:
-// also the item's 4 x 77 rows x 32 bytes of box sums, from the job's box-sum
-// planes straight into the slot's bound scratch (the layout flow_bound's steps
-// 2-4 read), under the caller's one vmcnt wait.  Window rows outside the job's
-// resident rows are outside the plane buffer's range too: zeros, and masked
-// like the window's.  Not loaded for an item the bound will not look at (an
-// h = B/2 item; the bypass state).  Returns whether the planes were loaded:
-// the bypass state may end between here and the item's bound phase, which then
-// forms the box sums itself.  The plane base and the job's offset are read
-// here only (no SGPRs across the task loop).
-template <int B, bool PL>
-__device__ __forceinline__ bool stage_item_wave(const SearchArgs& p, const QsadGeom& g, const Item& it,
-                                                uint8_t* buf, const FlowJobs& jb, FlowCtl* ctl) {
+// blocks, from its job's planes, under the caller's one vmcnt wait.  (The
+// job's box-sum planes are not staged: the bound phase loads what it reads of
+// them into registers, flow_plane_fetch below.)
+template <int B>
+__device__ __forceinline__ void stage_item_wave(const SearchArgs& p, const QsadGeom& g, const Item& it,
+                                                uint8_t* buf, const FlowJobs& jb) {
   const __amdgpu_buffer_rsrc_t rref =
       __builtin_amdgcn_make_buffer_rsrc((void*)jb.ref[it.j], (short)0, jb.ref_bytes[it.j], 0x00020000);
   const __amdgpu_buffer_rsrc_t rcur =
@@ -1025,31 +1018,6 @@ __device__ __forceinline__ bool stage_item_wave(const SearchArgs& p, const QsadG
           rcur, (__attribute__((address_space(3))) void*)(cur + s0), 16,
           cbase + (uint32_t)(((d >> 4) & 15) * stride + (d >> 8) * B), 0, 0, 0);
   }
-  if constexpr (PL) {
-    const int pf = __builtin_amdgcn_readfirstlane((int)ctl->pflags);
-    if (!(pf & PF_PLANES) || it.h != B) return false;
-    if ((pf & PF_BYPASS) &&
-        __builtin_amdgcn_readfirstlane(
-            (int)__hip_atomic_load(&ctl->run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= 4)
-      return false;
-    const int pp = jb.plane_pitch;
-    const __amdgpu_buffer_rsrc_t rpl = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(jb.planes + ((size_t)jb.plane_off64[it.j] << 6)), (short)0, jb.plane_rows[it.j] * 4 * pp,
-        0x00020000);
-    uint8_t* pr = buf + g.tile_bytes + 4 * B * B;
-    // LDS byte d = plane k, row r, half hf  <-  phase row 4 (prow0 - ref_row0 + r) + k
-    const uint32_t pbase = (uint32_t)((it.prow0 - jb.ref_row0[it.j]) * 4 * pp + ((it.X0 + 32) >> 2));
-    for (int s0 = 0; s0 < 4 * FLOW_PRUNE_PLANE; s0 += 1024) {
-      const int d = s0 + 16 * lane;
-      const int k = d / FLOW_PRUNE_PLANE, rem = d - k * FLOW_PRUNE_PLANE;
-      if (d < 4 * FLOW_PRUNE_PLANE)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rpl, (__attribute__((address_space(3))) void*)(pr + s0), 16,
-            pbase + (uint32_t)(((rem >> 5) * 4 + k) * pp + (rem & 16)), 0, 0, 0);
-    }
-    return true;
-  }
-  return false;
 }
 
 // Wave-tasks of one item: its lane-tasks (valid chunks x blocks x groups) / 64, rounded up.
@@ -1106,26 +1074,109 @@ __device__ __forceinline__ void lds_fence() {  // this wave's LDS writes before 
   __builtin_amdgcn_wave_barrier();
 }
 
+// ---- the bound's plane rows, from the job's box-sum planes (PF_PLANES) ----
+// In a launch with planes step 2 reads them from global memory (L2 / Infinity
+// Cache resident: the prepass wrote them in front of this launch), not from a
+// copy in the slot: lane (block b, phase k, dx groups 4m .. 4m + 3) loads the 8
+// bytes flow_plane_byte(.., yp, k, 4 b + 4 m) of every window row yp its
+// chunks read, each row once per item: a K = 13 row chunk reads the 25 rows
+// lc K .. lc K + 24, the next one carries the last 12 over and loads 13.  The
+// fold column's lane (block b, dy mod 16 = y) reads 4 bytes of phase 0 of the
+// rows y + 4 n.  The descriptor holds exactly the job's plane bytes: rows
+// above or below the job's resident ones read 0 and are masked like the
+// window's (no load straddles the end: flow_plane_loads_fit, host-checked).
+constexpr int FLOW_PLN_ROWS = 25, FLOW_PLN_FOLD = 20;
+struct FlowPlaneRegs {
+  uint32_t lo[FLOW_PLN_ROWS], hi[FLOW_PLN_ROWS];  // the chunk's rows, bytes 0-3 and 4-7
+  uint32_t f[FLOW_PLN_FOLD];                      // the fold column's rows y + 4 n
+};
+typedef uint32_t flow_u2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t flow_plane_rsrc(const FlowJobs& jb, int j) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(jb.planes + ((size_t)jb.plane_off64[j] << 6)), (short)0,
+                                           jb.plane_rows[j] * 4 * jb.plane_pitch, 0x00020000);
+}
+// N window rows from y0 on of the lane's phase k at `byte`
+template <int N>
+__device__ __forceinline__ void flow_plane_rows_load(__amdgpu_buffer_rsrc_t rs, int pp, int rel, int X0, int y0,
+                                                     int k, int byte, uint32_t (&lo)[N], uint32_t (&hi)[N],
+                                                     int at = 0) {
+  // The lane's part in one VGPR, the row's in an SGPR the compiler cannot
+  // follow: it otherwise keeps all N row offsets in VGPRs across the chunk loop.
+  const uint32_t lv = flow_plane_lane_byte(pp, k, byte);
+  uint32_t sr = flow_plane_row_byte(pp, rel, X0, y0);
+  asm volatile("" : "+s"(sr));
+#pragma unroll
+  for (int r = 0; r < N; r++) {
+    const flow_u2 v = __builtin_bit_cast(
+        flow_u2, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(lv + sr + (uint32_t)(4 * r * pp)), 0, 0));
+    lo[at + r] = v.x;
+    hi[at + r] = v.y;
+  }
+}
+__device__ __forceinline__ void flow_plane_fold_load(__amdgpu_buffer_rsrc_t rs, int pp, int rel, int X0, int lane,
+                                                     FlowPlaneRegs& R) {
+  const uint32_t lv = flow_plane_lane_byte(pp, 0, 4 * (lane >> 4) + 16) + (uint32_t)(4 * (lane & 15) * pp);
+  uint32_t sr = flow_plane_row_byte(pp, rel, X0, 0);
+  asm volatile("" : "+s"(sr));
+#pragma unroll
+  for (int n = 0; n < FLOW_PLN_FOLD; n++)  // window row (lane & 15) + 4 n
+    R.f[n] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(lv + sr + (uint32_t)(16 * n * pp)), 0, 0);
+}
+// Whether the staging wave issues the item's first plane loads with its window
+// DMA (so both land under the one vmcnt wait): not for an item the bound will
+// not look at (no planes in the launch, an h = B/2 item, the bypass state).
+// The bypass state may end between here and the bound, which then loads them.
+template <int B>
+__device__ __forceinline__ bool flow_plane_wanted(const Item& it, FlowCtl* ctl) {
+  const int pf = __builtin_amdgcn_readfirstlane((int)ctl->pflags);
+  if (!(pf & PF_PLANES) || it.h != B) return false;
+  return !((pf & PF_BYPASS) &&
+           __builtin_amdgcn_readfirstlane(
+               (int)__hip_atomic_load(&ctl->run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= 4);
+}
+// The first chunk's 25 rows.
+template <int B, int K>
+__device__ __forceinline__ void flow_plane_fetch(const Item& it, const FlowJobs& jb, FlowPlaneRegs& R) {
+  constexpr int S = 32;
+  static_assert(FLOW_PLN_ROWS == K + 12 && 4 * (FLOW_PLN_FOLD - 1) == 2 * S + 12, "rows a chunk, the fold column read");
+  const int lane = fresh_tid() & 63;
+  const int b = lane >> 4, k = (lane >> 2) & 3, m = lane & 3;
+  const int lc0 = max(0, (max(-S, -it.tly) + S) / K);
+  const __amdgpu_buffer_rsrc_t rs = flow_plane_rsrc(jb, it.j);
+  const int pp = jb.plane_pitch, rel = it.prow0 - jb.ref_row0[it.j];
+  flow_plane_rows_load<FLOW_PLN_ROWS>(rs, pp, rel, it.X0, lc0 * K, k, 4 * b + 4 * m, R.lo, R.hi);
+}
+__device__ __forceinline__ void flow_plane_zero(FlowPlaneRegs& R) {
+#pragma unroll
+  for (int r = 0; r < FLOW_PLN_ROWS; r++) R.lo[r] = R.hi[r] = 0;
+#pragma unroll
+  for (int n = 0; n < FLOW_PLN_FOLD; n++) R.f[n] = 0;
+}
+
+// R: the item's first plane rows where `fetched` (flow_plane_fetch, issued by
+// the caller in front of its wait for the window); else loaded here if the
+// launch has planes.
 template <int B, int K>
 __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& g, const Item& it,
                                            uint8_t* buf, uint64_t* keys, FlowCtl* ctl, int slot,
-                                           bool planes) {
+                                           const FlowJobs& jb, FlowPlaneRegs& R, bool fetched) {
   constexpr int S = 32, G = 16, TB = 4, P = 144;
   static_assert(B == 16 && K == 13, "bound scratch layout");
   const int lane = fresh_tid() & 63;
+  const int pf = __builtin_amdgcn_readfirstlane((int)ctl->pflags);
+  const bool planes = (pf & PF_PLANES) != 0;  // the slim scratch: no planes in the slot
   uint8_t* pr = buf + g.tile_bytes + TB * B * B;
-  uint16_t* list = reinterpret_cast<uint16_t*>(pr);  // overlays the planes (dead by then)
-  uint32_t* minlb = reinterpret_cast<uint32_t*>(pr + FLOW_PRUNE_MINLB);
-  uint32_t* qcur = reinterpret_cast<uint32_t*>(pr + FLOW_PRUNE_QCUR);
+  uint16_t* list = reinterpret_cast<uint16_t*>(pr);  // (overlays the slot's planes, dead by then)
+  uint32_t* minlb = reinterpret_cast<uint32_t*>(pr + (planes ? FLOW_SLIM_MINLB : FLOW_PRUNE_MINLB));
+  uint32_t* qcur = reinterpret_cast<uint32_t*>(pr + (planes ? FLOW_SLIM_QCUR : FLOW_PRUNE_QCUR));
   const uint32_t* cur = reinterpret_cast<const uint32_t*>(buf + g.tile_bytes);
   const int dymin = max(-S, -it.tly), dymax = min(S, p.height - it.h - it.tly);
   const int lc0 = max(0, (dymin + S) / K), lc1 = min(it.nch, (dymax + S) / K + 1);
   const int valid_lanes = (lc1 - lc0) * it.nb * G;
   const int nw = (valid_lanes + 63) >> 6;
-  const int pf = __builtin_amdgcn_readfirstlane((int)ctl->pflags);
   const bool verify = (pf & PF_VERIFY) != 0, stats = (pf & PF_STATS) != 0;
-  uint8_t* dead = pr + 640;                                   // verify: [320] flags
-  uint32_t* ub = reinterpret_cast<uint32_t*>(pr + 960);       // verify: U_b
+  uint8_t* dead = pr + FLOW_PRUNE_DEAD;                            // verify: [320] flags
+  uint32_t* ub = reinterpret_cast<uint32_t*>(pr + FLOW_PRUNE_UB);  // verify: U_b
 
   // Bypass: after 4 items in a row that stayed more than 3/4 live the bound is
   // skipped for 96 items, then ONE item probes again (run 3 -> 4 by
@@ -1167,10 +1218,11 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
   }
 
   // 1. box sums: the lane owns window columns x0, x0 + 1 and walks the 80 rows
-  // with a sliding 4-row sum of the packed horizontal 4-sums.  (Not when the
-  // staging wave's DMA brought the planes: the same bytes wherever a valid
-  // candidate reads them.)
-  if (!planes) {
+  // with a sliding 4-row sum of the packed horizontal 4-sums.  (Not in a
+  // launch with planes: the same bytes wherever a valid candidate reads them.)
+  if (planes) {
+    if (!fetched) flow_plane_fetch<B, K>(it, jb, R);
+  } else {
     const int x0 = 2 * lane, sh = x0 & 3;
     const uint8_t* src = buf + (x0 & ~3);
     uint8_t* dst = pr + sh * FLOW_PRUNE_PLANE + (x0 >> 2);  // planes sh and sh + 1
@@ -1220,22 +1272,22 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
       if (t < 2) mlo |= msk << (16 * t);
       else mhi |= msk << (16 * (t - 2));
     }
-    const uint8_t* pl = pr + k * FLOW_PRUNE_PLANE + 4 * b + 4 * m;
-#pragma unroll 1
-    for (int lc = lc0; lc < lc1; lc++) {
+    // One chunk: row(r, lo, hi) gives the lane's 8 bytes of window row lc K + r.
+    auto chunk = [&](int lc, auto row) {
       uint32_t clo = ~0u, chi = ~0u;
 #pragma unroll
       for (int j = 0; j < K; j++) {
         // No branch on the row's validity (a scalar mask instead): the chunk
-        // is straight-line code, so the 52 plane reads run ahead of the qsads.
+        // is straight-line code, so the plane reads run ahead of the qsads.
         // Rows past the valid range are real plane rows (Y <= 64), only masked.
         const int Y = lc * K + j;
         const uint32_t my = (Y >= Ylo && Y <= Yhi) ? 0u : ~0u;
         uint64_t acc = 0;
 #pragma unroll
         for (int sy = 0; sy < 4; sy++) {
-          const uint32_t* rp = reinterpret_cast<const uint32_t*>(pl + (Y + 4 * sy) * 32);
-          acc = __builtin_amdgcn_qsad_pk_u16_u8(((uint64_t)rp[1] << 32) | rp[0], qc[sy], acc);
+          uint32_t lo, hi;
+          row(j + 4 * sy, lo, hi);
+          acc = __builtin_amdgcn_qsad_pk_u16_u8(((uint64_t)hi << 32) | lo, qc[sy], acc);
         }
         clo = pk_min(clo, pk_key((uint32_t)acc, (uint32_t)j) | mlo | my);
         chi = pk_min(chi, pk_key((uint32_t)(acc >> 32), (uint32_t)j) | mhi | my);
@@ -1246,7 +1298,61 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
         if (e != 0xFFFFu)
           atomicMin(&minlb[(lc * TB + b) * G + 4 * m + t], ((e >> 4) << 7) | ((e & 15u) << 3) | (uint32_t)k);
       }
-    }
+    };
+    if (planes) {
+      // R holds the chunk's 25 rows.  The next chunk's 13 new rows are issued
+      // in front of this chunk's qsads and waited for behind them.
+      const __amdgpu_buffer_rsrc_t rs = flow_plane_rsrc(jb, it.j);
+      const int pp = jb.plane_pitch, rel = it.prow0 - jb.ref_row0[it.j];
+#pragma unroll 1
+      for (int lc = lc0; lc < lc1; lc++) {
+        uint32_t nlo[K], nhi[K];
+        if (lc + 1 < lc1) {
+          flow_plane_rows_load<K>(rs, pp, rel, it.X0, (lc + 1) * K + 12, k, 4 * b + 4 * m, nlo, nhi);
+        } else {
+#pragma unroll
+          for (int r = 0; r < K; r++) nlo[r] = nhi[r] = 0;
+        }
+        chunk(lc, [&](int r, uint32_t& lo, uint32_t& hi) {
+          lo = R.lo[r];
+          hi = R.hi[r];
+        });
+#pragma unroll
+        for (int r = 0; r < 12; r++) {
+          R.lo[r] = R.lo[K + r];
+          R.hi[r] = R.hi[K + r];
+        }
+#pragma unroll
+        for (int r = 0; r < K; r++) {
+          R.lo[12 + r] = nlo[r];
+          R.hi[12 + r] = nhi[r];
+        }
+      }
+      // the fold column dx = +S (phase 0, byte 4b + 16 ..): lane = (block, dy mod 16)
+      // (loaded here: held across the chunk loop, its 20 registers spilled)
+      flow_plane_fold_load(rs, pp, rel, it.X0, lane, R);
+      if (S <= dxmax) {
+#pragma unroll
+        for (int rr = 0; rr < 5; rr++) {
+          const int Y = (lane & 15) + 16 * rr;
+          if (Y <= 2 * S && Y >= Ylo && Y <= Yhi) {
+            uint32_t lb = 0;
+#pragma unroll
+            for (int sy = 0; sy < 4; sy++) lb = __builtin_amdgcn_sad_u8(R.f[4 * rr + sy], qc[sy], lb);
+            const int lc = Y / K, j = Y - lc * K;
+            atomicMin(&minlb[(lc * TB + b) * G + j], (lb << 7) | ((uint32_t)j << 3) | 4u);
+          }
+        }
+      }
+    } else {
+    const uint8_t* pl = pr + k * FLOW_PRUNE_PLANE + 4 * b + 4 * m;
+#pragma unroll 1
+    for (int lc = lc0; lc < lc1; lc++)
+      chunk(lc, [&](int r, uint32_t& lo, uint32_t& hi) {
+        const uint32_t* rp = reinterpret_cast<const uint32_t*>(pl + (lc * K + r) * 32);
+        lo = rp[0];
+        hi = rp[1];
+      });
     // the fold column dx = +S (plane 0, index 4b + 16 ..): lane = (block, dy mod 16)
     if (S <= dxmax) {
 #pragma unroll 1
@@ -1262,6 +1368,7 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
           atomicMin(&minlb[(lc * TB + b) * G + j], (lb << 7) | ((uint32_t)j << 3) | 4u);
         }
       }
+    }
     }
   }
   lds_fence();
@@ -1432,7 +1539,7 @@ __device__ __forceinline__ void flow_split_task(const SearchArgs& p, const QsadG
     atomicMin(reinterpret_cast<unsigned long long*>(&keys[b]),
               (unsigned long long)make_key(best >> 16, dx, dy));
     // Verify mode (see the unsplit task): per lane, by the entry's index.
-    if ((pfl & PF_VERIFY) && pv[640 + i] && (best >> 16) <= reinterpret_cast<const uint32_t*>(pv + 960)[b] &&
+    if ((pfl & PF_VERIFY) && pv[FLOW_PRUNE_DEAD + i] && (best >> 16) <= reinterpret_cast<const uint32_t*>(pv + FLOW_PRUNE_UB)[b] &&
         p.sched)
       __hip_atomic_store(p.sched + SCHED_ERR, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -1446,8 +1553,10 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
   // Pruning (flow_bound above) is compiled into the 144-byte-pitch instance
   // only: the planner turns it on for no other shape.
   const bool prune = PC == 144 && g.prune != 0;
-  const int NB = prune ? g.prune_slots : g.flow_slots;
-  const int slot_bytes = g.tile_bytes + g.tb * B * B + (prune ? FLOW_PRUNE_BYTES : 0);
+  // (a pruning launch with box-sum planes: the slim bound scratch, more slots)
+  const bool slim = prune && jb.planes != nullptr;
+  const int NB = !prune ? g.flow_slots : slim ? g.slim_slots : g.prune_slots;
+  const int slot_bytes = g.tile_bytes + g.tb * B * B + (!prune ? 0 : slim ? FLOW_SLIM_BYTES : FLOW_PRUNE_BYTES);
   uint64_t* keys = reinterpret_cast<uint64_t*>(smem + NB * slot_bytes);  // [NB][tb]
   FlowCtl* ctl = reinterpret_cast<FlowCtl*>(smem + NB * slot_bytes + NB * g.tb * 8);
   const int tid = (int)threadIdx.x, lane = tid & 63;
@@ -1494,12 +1603,20 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     for (int i = 0; i < wave; i++) __builtin_amdgcn_s_sleep(10);
     if (g.prio) __builtin_amdgcn_s_setprio(3);  // see me_fast_kernel
     const Item it0 = flow_item<B, K>(p, g, jb, tile_of(wave), -1);
-    const bool pl0 = stage_item_wave<B, PC == 144>(p, g, it0, smem + wave * slot_bytes, jb, ctl);
-    if (g.prio) __builtin_amdgcn_s_setprio(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stage_item_wave<B>(p, g, it0, smem + wave * slot_bytes, jb);
     if constexpr (PC == 144) {
+      // (the bound's first plane rows: issued here, landed by the same wait)
+      FlowPlaneRegs R;
+      const bool pl0 = prune && flow_plane_wanted<B>(it0, ctl);
+      if (pl0) flow_plane_fetch<B, K>(it0, jb, R);
+      else flow_plane_zero(R);
+      if (g.prio) __builtin_amdgcn_s_setprio(0);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if (prune)
-        flow_bound<B, K>(p, g, it0, smem + wave * slot_bytes, keys + wave * g.tb, ctl, wave, pl0);
+        flow_bound<B, K>(p, g, it0, smem + wave * slot_bytes, keys + wave * g.tb, ctl, wave, jb, R, pl0);
+    } else {
+      if (g.prio) __builtin_amdgcn_s_setprio(0);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     if (lane == 0)
       __hip_atomic_store(&ctl->ready[wave], (uint32_t)wave + 1u, __ATOMIC_RELEASE,
@@ -1511,7 +1628,7 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
   bool have = false;
 #ifdef ME_STAMPS
   // diagnostic build: per wave [start, first task, loop exit, spin cycles, tasks,
-  // realtime start, realtime end, hw_id] (tools/flow_stamps.py)
+  // realtime start, realtime end, hw_id | ring slots << 32] (tools/flow_stamps.py)
   const int fw = bid * 16 + wave;
   unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_first = 0, st_spin = 0, st_n = 0;
   const unsigned long long st_r0 = __builtin_amdgcn_s_memrealtime();
@@ -1712,7 +1829,7 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       // with SAD <= its block's U_b.
       if ((pfl & PF_VERIFY) && live && best < 0xFFFF0000u) {
         const uint8_t* pv = buf + g.tile_bytes + g.tb * B * B;
-        if (pv[640 + i] && (best >> 16) <= reinterpret_cast<const uint32_t*>(pv + 960)[b] && p.sched)
+        if (pv[FLOW_PRUNE_DEAD + i] && (best >> 16) <= reinterpret_cast<const uint32_t*>(pv + FLOW_PRUNE_UB)[b] && p.sched)
           __hip_atomic_store(p.sched + SCHED_ERR, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
@@ -1752,23 +1869,36 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
 #ifdef ME_STAMPS
         const unsigned long long st_d0 = __builtin_amdgcn_s_memtime();
 #endif
-        const bool pln = stage_item_wave<B, PC == 144>(p, g, itn, buf, jb, ctl);
-        if (g.prio) __builtin_amdgcn_s_setprio(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef ME_STAMPS
-        const unsigned long long st_d1 = __builtin_amdgcn_s_memtime();
-        st_dma += st_d1 - st_d0;
-#endif
+        stage_item_wave<B>(p, g, itn, buf, jb);
         if constexpr (PC == 144) {
+          FlowPlaneRegs R;
+          const bool pln = pfl && flow_plane_wanted<B>(itn, ctl);
+          if (pln) flow_plane_fetch<B, K>(itn, jb, R);
+          else flow_plane_zero(R);
+          if (g.prio) __builtin_amdgcn_s_setprio(0);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef ME_STAMPS
+          const unsigned long long st_d1 = __builtin_amdgcn_s_memtime();
+          st_dma += st_d1 - st_d0;
+          st_bound -= st_d1;
+#endif
           // (at raised issue priority: nothing of the item runs before its bound ends)
           if (pfl) {
             __builtin_amdgcn_s_setprio(3);
-            flow_bound<B, K>(p, g, itn, buf, keys + slot * g.tb, ctl, slot, pln);
+            flow_bound<B, K>(p, g, itn, buf, keys + slot * g.tb, ctl, slot, jb, R, pln);
             __builtin_amdgcn_s_setprio(0);
           }
+        } else {
+          if (g.prio) __builtin_amdgcn_s_setprio(0);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef ME_STAMPS
+          const unsigned long long st_d1 = __builtin_amdgcn_s_memtime();
+          st_dma += st_d1 - st_d0;
+          st_bound -= st_d1;
+#endif
         }
 #ifdef ME_STAMPS
-        st_bound += __builtin_amdgcn_s_memtime() - st_d1;
+        st_bound += __builtin_amdgcn_s_memtime();
         st_nb++;
 #endif
         if (lane == 0)
@@ -1791,7 +1921,8 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
     unsigned long long* o = g_stamps + 8 * fw;
     o[0] = st_t0; o[1] = st_first; o[2] = __builtin_amdgcn_s_memtime(); o[3] = st_spin;
-    o[4] = st_n; o[5] = st_r0; o[6] = __builtin_amdgcn_s_memrealtime(); o[7] = hw;
+    o[4] = st_n; o[5] = st_r0; o[6] = __builtin_amdgcn_s_memrealtime();
+    o[7] = hw | (unsigned long long)NB << 32;  // (the launch's ring slots above the hw id)
     // per wave, refills: [DMA wait cycles, bound cycles, refills]; executed
     // wave-tasks by class: [whole, 2, 4 lanes per entry] as count << 40 | cycles;
     // flow_item decodes at [the advance, the refill] likewise
@@ -2063,7 +2194,7 @@ static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const Sear
   // search when it holds every job's (attach_scratch sized it with
   // flow_planes_need; a captured search that met a smaller one runs without):
   // the prepass goes in front on the same stream.
-  if (g.pitch == 144 && g.prune && p.scratch && flow_planes_on(tuning(), jb.n)) {
+  if (g.pitch == 144 && g.prune && g.slim_slots && p.scratch && flow_planes_on(tuning(), jb.n)) {
     size_t off = 0;
     int max_rows = 0;
     bool ok = true;
@@ -2088,7 +2219,7 @@ static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const Sear
   // the ds_read2 offsets); any other pitch takes the runtime-pitch body
 #define ME_FLOW_CASE(PP)                                                                        \
   if (PP == 0 || g.pitch == PP) {                                                               \
-    const int lds = PP == 144 && g.prune ? g.prune_lds : g.lds;                                 \
+    const int lds = !(PP == 144 && g.prune) ? g.lds : jb.planes ? g.slim_lds : g.prune_lds;     \
     const hipError_t e = lds_attr((const void*)me_flow_kernel<16, 13, PP>, lds);                \
     if (e != hipSuccess) return e;                                                              \
     hipLaunchKernelGGL((me_flow_kernel<16, 13, PP>), dim3((unsigned)nwg), dim3(1024), lds,      \

@@ -390,6 +390,17 @@ bool plan_flow(const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g) {
       q.prune_split = tu.prune_split != 0;
       q.prune_slots = ns;
       q.prune_lds = ns * pslot + ns * q.tb * 8 + FLOW_CTL_BYTES;
+      // With box-sum planes the bound reads them from global memory and a slot
+      // carries FLOW_SLIM_BYTES (14,912 bytes a slot: 10 slots), if none of
+      // its plane loads can straddle a phase row's end.
+      const int sslot = slot + FLOW_SLIM_BYTES;
+      int sns = (FLOW_LDS - 16 * q.tb * 8 - FLOW_CTL_BYTES) / sslot;
+      if (sns > 16) sns = 16;  // FlowCtl's arrays
+      if (tu.flow_slots && tu.flow_slots < sns) sns = tu.flow_slots;
+      if (sns >= 2 && flow_plane_loads_fit(s.width, q.wg_per_row)) {
+        q.slim_slots = sns;
+        q.slim_lds = sns * sslot + sns * q.tb * 8 + FLOW_CTL_BYTES;
+      }
     }
   }
   return true;
@@ -454,7 +465,7 @@ size_t flow_planes_scratch(const PlanShape& s, int cus, const Tuning& tu, const 
       if ((uintptr_t)jobs[i].ref % 16 || (uintptr_t)jobs[i].cur % 16) return 0;
     }
     QsadGeom g;
-    if (!cached_plan(PLAN_FLOW, ps, cus, tu, &g, nullptr) || !g.prune) return 0;
+    if (!cached_plan(PLAN_FLOW, ps, cus, tu, &g, nullptr) || !g.prune || !g.slim_slots) return 0;
     size_t best = 0, sum = 0;  // the largest window of MAX_JOBS consecutive jobs
     for (int i = j0; i < j0 + m; i++) {
       sum += flow_plane_job_bytes(s.width, flow_plane_rows(jobs[i], s.blk, s.range, s.height));

@@ -2,7 +2,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 CC    ?= gcc
 CXX   ?= g++
-all: bin/mes_hip bin/mes_seq bin/valu_microbench bin/flow_planes_dump bin/flow_job_dump
+all: bin/mes_hip bin/mes_seq bin/valu_microbench bin/flow_planes_dump bin/flow_job_dump bin/flow_slim_dump
 
 # CPU harness of the launch tile -> job rule (me_geom.h alone)
 bin/flow_job_dump: tools/flow_job_dump.cc motionestimation_amd/csrc/me_geom.h
@@ -14,6 +14,11 @@ CSRC = motionestimation_amd/csrc
 bin/flow_planes_dump: tools/flow_planes_dump.cc $(CSRC)/me_valu_plan.cpp $(CSRC)/me_geom.h $(CSRC)/me_tuning.h
 	mkdir -p bin
 	$(CXX) -O1 -std=c++17 -Wall -I$(CSRC) -o $@ tools/flow_planes_dump.cc $(CSRC)/me_valu_plan.cpp -lpthread
+
+# CPU harness of the pruning flow launch's two scratch layouts and the bound's plane loads
+bin/flow_slim_dump: tools/flow_slim_dump.cc $(CSRC)/me_valu_plan.cpp $(CSRC)/me_geom.h $(CSRC)/me_tuning.h
+	mkdir -p bin
+	$(CXX) -O1 -std=c++17 -Wall -I$(CSRC) -o $@ tools/flow_slim_dump.cc $(CSRC)/me_valu_plan.cpp -lpthread
 
 bin/mes_hip: tools/mes_main.c include/me.h motionestimation_amd/lib/libme_hip.so
 	mkdir -p bin

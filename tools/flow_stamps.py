@@ -75,7 +75,9 @@ print(f"clock (GHz): median {np.median(clk):.3f}")
 # b runs on XCD b % 8 (round-robin dispatch).  Per SIMD: idle before its first
 # task (from the kernel's first wave start) and after its last wave ends (to
 # the kernel's last wave end), in us of realtime.
-hw = st[:, 7]
+hw = st[:, 7] & 0xFFFFFFFF
+if (st[:, 7] >> 32).any():  # (a stamps build from before the slot count was recorded leaves 0)
+    print(f"ring slots of the launch: {int((st[:, 7] >> 32).max())}")
 simd = (hw >> 4) & 3
 kend = r1.max()
 first_rt = r0 + (first - start) / np.maximum(clk, 1e-3) / 10.0  # cycles -> 10 ns ticks
