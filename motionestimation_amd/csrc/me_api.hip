@@ -80,6 +80,8 @@ static Tuning read_tuning() {
   env_int("ME_PRUNE_BYPASS", 0, 1, &t.prune_bypass);
   env_int("ME_PRUNE_PLANES", 0, 1, &t.prune_planes);
   env_int("ME_PRUNE_SPLIT", 0, 1, &t.prune_split);
+  env_int("ME_FLOW_TABLE", 0, 1, &t.flow_table);
+  env_int("ME_FLOW_TABLE_CAP", 1, 4096, &t.flow_table_cap);
   t.prune_stats = 1;
   env_int("ME_MFMA_BATCH", 0, 1, &t.mfma_batch);
   env_int("ME_MFMA_S2K", 0, 1, &t.mfma_s2k);
@@ -800,6 +802,9 @@ extern "C" int me_debug_prune_stats(me_ctx* c, uint32_t* out4) {
   (void)hipSetDevice(prev);
   return rc;
 }
+// ... the LDS item table of the process's last flow launch with box-sum planes:
+// its entries, 0 if that launch ran without a table, -1 before any such launch.
+extern "C" int me_debug_flow_table(void) { return me::last_flow_table(); }
 // ... and the executed wave-tasks of pruned launches by split class: run whole
 // (P = 1), with 2 and with 4 lanes per list entry (me_geom.h flow_split_parts).
 extern "C" int me_debug_prune_split_stats(me_ctx* c, uint32_t* out3) {

@@ -239,6 +239,17 @@ ME_HOST_DEVICE inline int flow_job_from(const FlowJobs& jb, int tile, int j0) {
   while (j + 1 < jb.n && jb.tile_pre[j + 1] <= tile) j++;
   return j;
 }
+// (the bisection over any copy of tile_pre: the item table's builders read one in LDS)
+ME_HOST_DEVICE inline int flow_job_find_in(const int* tile_pre, int n, int tile) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (tile_pre[mid + 1] > tile) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+// (written out, not through the pointer form: the kernels read jb from their arguments)
 ME_HOST_DEVICE inline int flow_job_find(const FlowJobs& jb, int tile) {
   int lo = 0, hi = jb.n - 1;
   while (lo < hi) {
@@ -247,6 +258,98 @@ ME_HOST_DEVICE inline int flow_job_find(const FlowJobs& jb, int tile) {
     else lo = mid + 1;
   }
   return lo;
+}
+
+// ---- the flow kernel's items (me_flow_kernel) ----
+// Geometry of one work item = (tile of TB blocks, dy pass); j: the flow
+// kernel's job (FlowJobs) the tile belongs to.
+struct Item {
+  int bx0, by, nb, tly, h, a, X0, c0, nch, prow0, prows, j;
+};
+// A workgroup's items: the XCD band of bid % 8 (a speed heuristic only), member
+// m = bid / 8 takes tiles band0 + m, + n_x, ... (every job's tiles, job-major).
+struct FlowWalk {
+  int tile0, step, nitems;  // item k is launch tile tile0 + k * step
+};
+ME_HOST_DEVICE inline FlowWalk flow_walk(int ntiles, int nwg, int bid) {
+  const int ng = nwg < 8 ? nwg : 8;
+  const int x = bid % ng, m = bid / ng;
+  const int n_x = nwg / ng + (x < nwg % ng ? 1 : 0);
+  const int band0 = (int)((long)ntiles * x / ng), band1 = (int)((long)ntiles * (x + 1) / ng);
+  FlowWalk w;
+  w.tile0 = band0 + m;
+  w.step = n_x;
+  w.nitems = band1 - band0 > m ? (band1 - band0 - m + n_x - 1) / n_x : 0;
+  return w;
+}
+// The item table of a pruning launch with box-sum planes: the workgroup decodes
+// its items once, in front of its start barrier, into LDS behind its control
+// block; the waves then place a pulled task by the prefixes and rebuild the
+// item from the packed word, with no job-table load.  Entry k: the index of
+// item k's first wave-task (entry nitems: the workgroup's task count) and
+// job | tile column << 5 | absolute block row << 16.
+struct FlowEntry {
+  uint32_t pre, pack;
+};
+constexpr int FLOW_ENTRY_BYTES = 8;
+static_assert(sizeof(FlowEntry) == FLOW_ENTRY_BYTES, "LDS layout of the item table");
+static_assert(MAX_JOBS <= 32, "the packed word gives the job 5 bits");
+ME_HOST_DEVICE inline uint32_t flow_entry_pack(int j, int col, int by) {
+  return (uint32_t)j | (uint32_t)col << 5 | (uint32_t)by << 16;
+}
+// The item of job j at block row by, first block bx0 (all dy chunks: one
+// pass): what job_item_at gives for the tile (row-major tiles, strip_w == 0).
+ME_HOST_DEVICE inline Item flow_item_make(const SearchArgs& p, const QsadGeom& g, int B, int K, int j,
+                                          int by, int bx0) {
+  Item it;
+  it.j = j;
+  it.bx0 = bx0;
+  it.by = by;
+  it.nb = g.tb < g.nbx_full - bx0 ? g.tb : g.nbx_full - bx0;
+  it.tly = by * B;
+  it.h = B < p.height - it.tly ? B : p.height - it.tly;
+  it.a = ((bx0 * B - p.range) % 4 + 4) % 4;
+  it.X0 = bx0 * B - p.range - it.a;
+  it.c0 = 0;
+  it.nch = g.cpp < g.chunks ? g.cpp : g.chunks;
+  it.prow0 = it.tly - p.range;
+  it.prows = it.nch * K + B - 1;
+  return it;
+}
+ME_HOST_DEVICE inline Item flow_entry_item(const SearchArgs& p, const QsadGeom& g, int B, int K, uint32_t pack) {
+  return flow_item_make(p, g, B, K, (int)(pack & 31u), (int)(pack >> 16), (int)((pack >> 5) & 2047u) * g.tb);
+}
+// Launch tile `tile` of job j (rows from r0j, tiles from prej) packed.
+ME_HOST_DEVICE inline uint32_t flow_entry_of(const QsadGeom& g, int tile, int j, int prej, int r0j) {
+  const int t = tile - prej, row = t / g.wg_per_row;
+  return flow_entry_pack(j, t - row * g.wg_per_row, r0j + row);
+}
+// Wave-tasks of one item: its lane-tasks (valid chunks x blocks x groups) / 64,
+// rounded up; *lc0_out: its first valid chunk (the dy clamp at the frame's top).
+ME_HOST_DEVICE inline int flow_item_tasks(const SearchArgs& p, const QsadGeom& g, int K, const Item& it,
+                                          int* lc0_out) {
+  const int S = p.range;
+  const int dymin = -S > -it.tly ? -S : -it.tly;
+  const int top = p.height - it.h - it.tly, dymax = S < top ? S : top;
+  const int a = (dymin + S) / K, b = (dymax + S) / K + 1;
+  const int lc0 = a > 0 ? a : 0, lc1 = it.nch < b ? it.nch : b;
+  *lc0_out = lc0;
+  return ((lc1 - lc0) * it.nb * g.groups + 63) >> 6;
+}
+// Entries the launch's table needs (the longest walk's items and the end
+// entry), or 0: no table (it does not fit `room` bytes, a field does not fit
+// its bits, the tiles walk in strips, or more items than cap > 0 allows: the
+// tuning build's way to the path without a table).
+inline int flow_table_entries(const QsadGeom& g, int ntiles, int nwg, int max_by, int room, int cap) {
+  if (nwg < 1 || ntiles < 1) return 0;
+  int most = 0;
+  for (int bid = 0; bid < nwg; bid++) {
+    const int n = flow_walk(ntiles, nwg, bid).nitems;
+    if (n > most) most = n;
+  }
+  if (g.strip_w > 0 || g.wg_per_row > 2048 || max_by >= 65536) return 0;
+  if (cap > 0 && most > cap) return 0;
+  return (most + 1) * FLOW_ENTRY_BYTES <= room ? most + 1 : 0;
 }
 
 // ---- box-sum planes of the pruning flow plan (S = 32, 4-block tiles) ----

@@ -66,6 +66,7 @@ hipError_t launch_jobs(const SearchArgs& base, const SearchJob* jobs, int n, hip
 // Scratch bytes the flow launches of launch_jobs(base, jobs, n) want for their
 // box-sum planes (flow_planes_scratch, me_valu_plan.cpp, for this device and
 // tuning; 0: none).  A search lent less runs without planes.
+int last_flow_table();  // entries of the last planes launch's LDS item table (0: it ran without; -1: no such launch yet)
 size_t flow_planes_need(const SearchArgs& base, const SearchJob* jobs, int n);
 
 // Matrix-core SSD path (me_mfma.hip, me_band.hip).  MfmaGeom, MfmaJobs and the

@@ -18,7 +18,8 @@
 //                          horizontal x K vertical candidates of one block and
 //                          walks the window rows, 16 |a-b| per v_qsad_pk_u16_u8
 //                          with the cur block held in VGPRs.
-//   me_flow_kernel<B, K, PC>
+//   me_flow_kernel<B, K, PC>, me_flow_chain_kernel<B, K> (me_flow_kernel.inc,
+//                          compiled twice; the second: pruning launches with box-sum planes)
 //                          SAD, 16x16, S = 32 on frames with >= 2 tiles per CU
 //                          (the 1080p headline): one 1,024-thread workgroup
 //                          per CU, a ring of LDS slots, waves pulling 64-lane
@@ -274,10 +275,21 @@ __device__ unsigned long long g_stamps[8 << 16];
 // ... and per wave of me_fast_kernel: [start, first item staged, last task
 // loop done, end, hw_id, xcc_id, realtime start, realtime end] (tools/wave_stamps.py)
 __device__ unsigned long long g_wstamps[8 << 14];
+// The flow kernel's bound phase per wave (refills only), cycles summed: [cur q
+// and minlb init, step 2's chunks, chunks run, the fold column, step 3, step 4,
+// items bounded, step 3's wait for the window DMA] (tools/flow_stamps.py).
+__device__ unsigned long long g_bstamps[16 << 14];
+// ... words 8, 9: cycles from a slot's publish (the release store of `ready`)
+// to the start of the first executed wave-task of its item, summed over the
+// items this wave completed, and their count.  g_pub / g_first: per workgroup
+// and slot, the publish time and the earliest executed task's start.
+__device__ unsigned long long g_pub[16 << 12], g_first[16 << 12];
+#define ME_BSTAMP(i) do { if (bs) { const unsigned long long bnow = __builtin_amdgcn_s_memtime(); bs[i] += bnow - bt; bt = bnow; } } while (0)
 #define ME_WSTAMP(slot, v) do { if ((threadIdx.x & 63) == 0 && wwid < (1 << 14)) g_wstamps[8 * wwid + (slot)] = (v); } while (0)
 #else
 #define ME_WSTAMP(slot, v) do { } while (0)
 #define ME_STAMP(slot, v) do { } while (0)
+#define ME_BSTAMP(i) do { } while (0)
 #endif
 
 // 32-bit lane keys (sad << 16 | j*5 + i) ordered like (cost, dy, dx); i = 4 is
@@ -506,12 +518,7 @@ __device__ __forceinline__ void dma4(__amdgpu_buffer_rsrc_t rs, uint8_t* lds_dst
   }
 }
 
-// Geometry of one work item = (tile of TB blocks, dy pass); j: the flow
-// kernel's job (FlowJobs) the tile belongs to.
-struct Item {
-  int bx0, by, nb, tly, h, a, X0, c0, nch, prow0, prows, j;
-};
-
+// One work item (Item, me_geom.h) = (tile of TB blocks, dy pass).
 template <int B, int K>
 __device__ __forceinline__ Item item_of(const SearchArgs& p, const QsadGeom& g, int tile,
                                         int pass) {
@@ -967,7 +974,11 @@ struct FlowCtl {
 // its step 1 and loads the plane rows of step 2 from them (the slim scratch).
 // PF_SPLIT: a pruned item's wave-task of <= 32 list entries is split by rows
 // (flow_split_task below).
-enum { PF_ON = 1, PF_VERIFY = 2, PF_BYPASS = 4, PF_STATS = 8, PF_PLANES = 16, PF_SPLIT = 32 };
+// PF_TABLE: the workgroup's items are decoded in the LDS item table behind this
+// block (me_geom.h FlowEntry).  PF_EARLY: a slot's fill issues the window DMA
+// last and starts the bound under it (flow_fill below).
+enum { PF_ON = 1, PF_VERIFY = 2, PF_BYPASS = 4, PF_STATS = 8, PF_PLANES = 16, PF_SPLIT = 32, PF_TABLE = 64,
+       PF_EARLY = 128 };
 static_assert(sizeof(FlowCtl) <= FLOW_CTL_BYTES, "control block of the pruning launch");
 
 // Tile of the flow kernel's launch -> its item (all dy chunks: one pass).  A
@@ -1020,10 +1031,60 @@ __device__ __forceinline__ void stage_item_wave(const SearchArgs& p, const QsadG
   }
 }
 
+// The chain kernel stages an item in parts (flow_fill): stage_item_wave's two loops apart.
+// WHAT: bit 0 the window, bit 1 the cur blocks (window first where both).
+// STEPS > 0: the window in exactly STEPS DMA instructions (the caller checked
+// that the item's bytes end in the last of them), so that a vmcnt(STEPS) behind
+// them waits for everything issued in front and for nothing of the window.
+constexpr int FLOW_STAGE_WIN = 1, FLOW_STAGE_CUR = 2;
+template <int B, int WHAT, int STEPS = 0>
+__device__ __forceinline__ void stage_item_part(const SearchArgs& p, const QsadGeom& g, const Item& it,
+                                                uint8_t* buf, const FlowJobs& jb) {
+  const __amdgpu_buffer_rsrc_t rref =
+      __builtin_amdgcn_make_buffer_rsrc((void*)jb.ref[it.j], (short)0, jb.ref_bytes[it.j], 0x00020000);
+  const __amdgpu_buffer_rsrc_t rcur =
+      __builtin_amdgcn_make_buffer_rsrc((void*)jb.cur[it.j], (short)0, jb.cur_bytes[it.j], 0x00020000);
+  // lane recomputed per call (fresh_tid): hoisted lane-derived offsets spilled
+  const int lane = fresh_tid() & 63;
+  uint8_t* tile = buf;
+  uint8_t* cur = buf + g.tile_bytes;
+  const int pitch = g.pitch, stride = p.stride;
+  if constexpr ((WHAT & FLOW_STAGE_WIN) != 0) {
+    const uint32_t base = (uint32_t)((it.prow0 - jb.ref_row0[it.j]) * stride + it.X0);
+    const int bytes = it.prows * pitch;
+    auto step = [&](int s0) {  // 16-byte granules (g.tile16)
+      const int d = s0 + 16 * lane;
+      const int r = (int)__umulhi((uint32_t)d, g.pitch_magic), x = d - r * pitch;
+      if (d < bytes)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            rref, (__attribute__((address_space(3))) void*)(tile + s0), 16,
+            base + (uint32_t)(r * stride + x), 0, 0, 0);
+    };
+    if constexpr (STEPS > 0) {
+#pragma unroll
+      for (int i = 0; i < STEPS; i++) step(1024 * i);
+    } else {
+      for (int s0 = 0; s0 < bytes; s0 += 1024) step(s0);
+    }
+  }
+  if constexpr ((WHAT & FLOW_STAGE_CUR) != 0) {
+    const uint32_t cbase = (uint32_t)((it.tly - jb.cur_row0[it.j]) * stride + it.bx0 * B);
+    const int cb = it.nb * B * B;
+    for (int s0 = 0; s0 < cb; s0 += 1024) {
+      const int d = s0 + 16 * lane;
+      if (d < cb)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            rcur, (__attribute__((address_space(3))) void*)(cur + s0), 16,
+            cbase + (uint32_t)(((d >> 4) & 15) * stride + (d >> 8) * B), 0, 0, 0);
+    }
+  }
+}
+
 // Wave-tasks of one item: its lane-tasks (valid chunks x blocks x groups) / 64, rounded up.
 template <int B, int K>
 __device__ __forceinline__ int flow_tasks(const SearchArgs& p, const QsadGeom& g, const Item& it,
                                           int* lc0_out) {
+  // (flow_item_tasks of me_geom.h, the item table's count, is this rule: tests/test_flow_item_table.py)
   const int S = p.range;
   const int dymin = max(-S, -it.tly), dymax = min(S, p.height - it.h - it.tly);
   const int lc0 = max(0, (dymin + S) / K), lc1 = min(it.nch, (dymax + S) / K + 1);
@@ -1086,6 +1147,11 @@ __device__ __forceinline__ void lds_fence() {  // this wave's LDS writes before 
 // above or below the job's resident ones read 0 and are masked like the
 // window's (no load straddles the end: flow_plane_loads_fit, host-checked).
 constexpr int FLOW_PLN_ROWS = 25, FLOW_PLN_FOLD = 20;
+#ifdef ME_FLOW_STREAM  // the A/B build of the chain kernel's streamed step 2 (Makefile `stream`)
+constexpr bool FLOW_STREAM = true;
+#else
+constexpr bool FLOW_STREAM = false;
+#endif
 struct FlowPlaneRegs {
   uint32_t lo[FLOW_PLN_ROWS], hi[FLOW_PLN_ROWS];  // the chunk's rows, bytes 0-3 and 4-7
   uint32_t f[FLOW_PLN_FOLD];                      // the fold column's rows y + 4 n
@@ -1096,15 +1162,18 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t flow_plane_rsrc(const FlowJobs
                                            jb.plane_rows[j] * 4 * jb.plane_pitch, 0x00020000);
 }
 // N window rows from y0 on of the lane's phase k at `byte`
-template <int N>
+template <int N, bool CHAIN = false>
 __device__ __forceinline__ void flow_plane_rows_load(__amdgpu_buffer_rsrc_t rs, int pp, int rel, int X0, int y0,
                                                      int k, int byte, uint32_t (&lo)[N], uint32_t (&hi)[N],
                                                      int at = 0) {
   // The lane's part in one VGPR, the row's in an SGPR the compiler cannot
   // follow: it otherwise keeps all N row offsets in VGPRs across the chunk loop.
-  const uint32_t lv = flow_plane_lane_byte(pp, k, byte);
+  // (The chain kernel: the lane's part opaque as well, else lane part + row
+  // step, which no chunk changes, is hoisted out of its chunk loop as N more VGPRs.)
+  uint32_t lv = flow_plane_lane_byte(pp, k, byte);
   uint32_t sr = flow_plane_row_byte(pp, rel, X0, y0);
   asm volatile("" : "+s"(sr));
+  if constexpr (CHAIN) asm volatile("" : "+v"(lv));
 #pragma unroll
   for (int r = 0; r < N; r++) {
     const flow_u2 v = __builtin_bit_cast(
@@ -1135,7 +1204,7 @@ __device__ __forceinline__ bool flow_plane_wanted(const Item& it, FlowCtl* ctl) 
                (int)__hip_atomic_load(&ctl->run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= 4);
 }
 // The first chunk's 25 rows.
-template <int B, int K>
+template <int B, int K, bool CHAIN = false>
 __device__ __forceinline__ void flow_plane_fetch(const Item& it, const FlowJobs& jb, FlowPlaneRegs& R) {
   constexpr int S = 32;
   static_assert(FLOW_PLN_ROWS == K + 12 && 4 * (FLOW_PLN_FOLD - 1) == 2 * S + 12, "rows a chunk, the fold column read");
@@ -1144,7 +1213,7 @@ __device__ __forceinline__ void flow_plane_fetch(const Item& it, const FlowJobs&
   const int lc0 = max(0, (max(-S, -it.tly) + S) / K);
   const __amdgpu_buffer_rsrc_t rs = flow_plane_rsrc(jb, it.j);
   const int pp = jb.plane_pitch, rel = it.prow0 - jb.ref_row0[it.j];
-  flow_plane_rows_load<FLOW_PLN_ROWS>(rs, pp, rel, it.X0, lc0 * K, k, 4 * b + 4 * m, R.lo, R.hi);
+  flow_plane_rows_load<FLOW_PLN_ROWS, CHAIN>(rs, pp, rel, it.X0, lc0 * K, k, 4 * b + 4 * m, R.lo, R.hi);
 }
 __device__ __forceinline__ void flow_plane_zero(FlowPlaneRegs& R) {
 #pragma unroll
@@ -1156,11 +1225,15 @@ __device__ __forceinline__ void flow_plane_zero(FlowPlaneRegs& R) {
 // R: the item's first plane rows where `fetched` (flow_plane_fetch, issued by
 // the caller in front of its wait for the window); else loaded here if the
 // launch has planes.
-template <int B, int K>
+template <int B, int K, bool CHAIN = false>
 __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& g, const Item& it,
                                            uint8_t* buf, uint64_t* keys, FlowCtl* ctl, int slot,
-                                           const FlowJobs& jb, FlowPlaneRegs& R, bool fetched) {
+                                           const FlowJobs& jb, FlowPlaneRegs& R, bool fetched,
+                                           unsigned long long* bs = nullptr) {
   constexpr int S = 32, G = 16, TB = 4, P = 144;
+#ifdef ME_STAMPS
+  unsigned long long bt = __builtin_amdgcn_s_memtime();  // (bs: the stamps build's split of a refill's bound)
+#endif
   static_assert(B == 16 && K == 13, "bound scratch layout");
   const int lane = fresh_tid() & 63;
   const int pf = __builtin_amdgcn_readfirstlane((int)ctl->pflags);
@@ -1221,7 +1294,7 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
   // with a sliding 4-row sum of the packed horizontal 4-sums.  (Not in a
   // launch with planes: the same bytes wherever a valid candidate reads them.)
   if (planes) {
-    if (!fetched) flow_plane_fetch<B, K>(it, jb, R);
+    if (!fetched) flow_plane_fetch<B, K, CHAIN>(it, jb, R);
   } else {
     const int x0 = 2 * lane, sh = x0 & 3;
     const uint8_t* src = buf + (x0 & ~3);
@@ -1253,6 +1326,7 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
     for (int r = 0; r < 5; r++) minlb[64 * r + lane] = ~0u;
   }
   lds_fence();
+  ME_BSTAMP(0);
 
   const int b = lane >> 4;
   const int dxmin = max(-S, -(it.bx0 + b) * B), dxmax = min(S, p.width - B - (it.bx0 + b) * B);
@@ -1304,11 +1378,105 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
       // in front of this chunk's qsads and waited for behind them.
       const __amdgpu_buffer_rsrc_t rs = flow_plane_rsrc(jb, it.j);
       const int pp = jb.plane_pitch, rel = it.prow0 - jb.ref_row0[it.j];
+      if constexpr (CHAIN && FLOW_STREAM) {
+        // Step 2 streamed: the -DME_FLOW_STREAM A/B build (Makefile `stream`;
+        // DESIGN.md, the item-chain paragraph), not the product.  A plane row is
+        // used by its four qsads as it lands and its registers take the row two
+        // 13-row groups ahead.  Row r adds qsad(row r, qc[sy]) to candidate row
+        // dy = r - 4 sy: a ring of 13 packed accumulators, dy complete at row
+        // dy + 12 and merged like a chunk's row j = dy mod 13 (same keys, same
+        // entries).  The fold column is loaded behind the groups.
+        uint32_t alo[K], ahi[K], nlo[K], nhi[K];
+#pragma unroll
+        for (int r = 0; r < K; r++) {
+          alo[r] = R.lo[r];
+          ahi[r] = R.hi[r];
+        }
+#pragma unroll
+        for (int r = 0; r < 12; r++) {
+          nlo[r] = R.lo[K + r];
+          nhi[r] = R.hi[K + r];
+        }
+        {
+          uint32_t t1[1], t2[1];
+          flow_plane_rows_load<1, true>(rs, pp, rel, it.X0, lc0 * K + 25, k, 4 * b + 4 * m, t1, t2);
+          nlo[12] = t1[0];
+          nhi[12] = t2[0];
+        }
+        uint64_t acc[K];
+#pragma unroll
+        for (int r = 0; r < K; r++) acc[r] = 0;
+        uint32_t clo = ~0u, chi = ~0u;
+        // one group: rows c K .. c K + 12 from (xlo, xhi), refilled with group c + 2's
+        auto group = [&](int c, uint32_t (&xlo)[K], uint32_t (&xhi)[K]) {
+          uint32_t lv = flow_plane_lane_byte(pp, k, 4 * b + 4 * m);
+          // (past the last group: an offset no descriptor holds, the loads return 0)
+          uint32_t sr = c + 2 <= lc1 ? flow_plane_row_byte(pp, rel, it.X0, (c + 2) * K) : 0x80000000u;
+          asm volatile("" : "+s"(sr));
+          asm volatile("" : "+v"(lv));
+#pragma unroll
+          for (int j = 0; j < K; j++) {
+            const uint64_t row = ((uint64_t)xhi[j] << 32) | xlo[j];
+            acc[j] = __builtin_amdgcn_qsad_pk_u16_u8(row, qc[0], 0);
+            acc[(j + K - 4) % K] = __builtin_amdgcn_qsad_pk_u16_u8(row, qc[1], acc[(j + K - 4) % K]);
+            acc[(j + K - 8) % K] = __builtin_amdgcn_qsad_pk_u16_u8(row, qc[2], acc[(j + K - 8) % K]);
+            acc[(j + K - 12) % K] = __builtin_amdgcn_qsad_pk_u16_u8(row, qc[3], acc[(j + K - 12) % K]);
+            {
+              const flow_u2 v = __builtin_bit_cast(
+                  flow_u2, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(lv + sr + (uint32_t)(4 * j * pp)), 0, 0));
+              xlo[j] = v.x;
+              xhi[j] = v.y;
+            }
+            // complete: dy = c K + j - 12, row idx of chunk cc
+            const int cc = j == 12 ? c : c - 1, idx = j == 12 ? 0 : j + 1;
+            const int Y = c * K + j - 12;
+            const uint32_t my = (Y >= Ylo && Y <= Yhi) ? 0u : ~0u;
+            const uint64_t a = acc[(j + K - 12) % K];
+            clo = pk_min(clo, pk_key((uint32_t)a, (uint32_t)idx) | mlo | my);
+            chi = pk_min(chi, pk_key((uint32_t)(a >> 32), (uint32_t)idx) | mhi | my);
+            if (j == 11) {  // chunk c - 1 is complete
+#pragma unroll
+              for (int t = 0; t < 4; t++) {
+                const uint32_t e = ((t < 2 ? clo : chi) >> (16 * (t & 1))) & 0xFFFFu;
+                if (e != 0xFFFFu)
+                  atomicMin(&minlb[(cc * TB + b) * G + 4 * m + t], ((e >> 4) << 7) | ((e & 15u) << 3) | (uint32_t)k);
+              }
+              clo = chi = ~0u;
+            }
+          }
+        };
+        // groups lc0 .. lc1: the last one completes chunk lc1 - 1 (its row 12
+        // starts a chunk past the valid ones: masked)
 #pragma unroll 1
-      for (int lc = lc0; lc < lc1; lc++) {
+        for (int c = lc0; c <= lc1; c += 2) {
+          group(c, alo, ahi);
+          if (c + 1 <= lc1) group(c + 1, nlo, nhi);
+        }
+        ME_BSTAMP(1);
+#ifdef ME_STAMPS
+        if (bs) bs[2] += (unsigned long long)(lc1 - lc0);
+#endif
+        flow_plane_fold_load(rs, pp, rel, it.X0, lane, R);
+        if (S <= dxmax) {
+#pragma unroll
+          for (int rr = 0; rr < 5; rr++) {
+            const int Y = (lane & 15) + 16 * rr;
+            if (Y <= 2 * S && Y >= Ylo && Y <= Yhi) {
+              uint32_t lb = 0;
+#pragma unroll
+              for (int sy = 0; sy < 4; sy++) lb = __builtin_amdgcn_sad_u8(R.f[4 * rr + sy], qc[sy], lb);
+              const int lc = Y / K, j = Y - lc * K;
+              atomicMin(&minlb[(lc * TB + b) * G + j], (lb << 7) | ((uint32_t)j << 3) | 4u);
+            }
+          }
+        }
+      } else {
+      // (the chain kernel runs its last chunk apart from the loop, below)
+#pragma unroll 1
+      for (int lc = lc0; lc + (CHAIN ? 1 : 0) < lc1; lc++) {
         uint32_t nlo[K], nhi[K];
-        if (lc + 1 < lc1) {
-          flow_plane_rows_load<K>(rs, pp, rel, it.X0, (lc + 1) * K + 12, k, 4 * b + 4 * m, nlo, nhi);
+        if (CHAIN || lc + 1 < lc1) {
+          flow_plane_rows_load<K, CHAIN>(rs, pp, rel, it.X0, (lc + 1) * K + 12, k, 4 * b + 4 * m, nlo, nhi);
         } else {
 #pragma unroll
           for (int r = 0; r < K; r++) nlo[r] = nhi[r] = 0;
@@ -1328,9 +1496,24 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
           R.hi[12 + r] = nhi[r];
         }
       }
-      // the fold column dx = +S (phase 0, byte 4b + 16 ..): lane = (block, dy mod 16)
-      // (loaded here: held across the chunk loop, its 20 registers spilled)
+      // The chain kernel's last chunk has no rows to fetch ahead: the fold
+      // column's 20 loads go out in their place, under its qsads.  (Issued
+      // behind the chunks they cost a global load's latency of their own;
+      // issued in front of them their registers, live across every chunk, spilled.)
+      if constexpr (!CHAIN) ME_BSTAMP(1);
       flow_plane_fold_load(rs, pp, rel, it.X0, lane, R);
+      if constexpr (CHAIN) {
+        if (lc1 > lc0)
+          chunk(lc1 - 1, [&](int r, uint32_t& lo, uint32_t& hi) {
+            lo = R.lo[r];
+            hi = R.hi[r];
+          });
+        ME_BSTAMP(1);
+      }
+#ifdef ME_STAMPS
+      if (bs) bs[2] += (unsigned long long)(lc1 - lc0);
+#endif
+      // the fold column dx = +S (phase 0, byte 4b + 16 ..): lane = (block, dy mod 16)
       if (S <= dxmax) {
 #pragma unroll
         for (int rr = 0; rr < 5; rr++) {
@@ -1343,6 +1526,7 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
             atomicMin(&minlb[(lc * TB + b) * G + j], (lb << 7) | ((uint32_t)j << 3) | 4u);
           }
         }
+      }
       }
     } else {
     const uint8_t* pl = pr + k * FLOW_PRUNE_PLANE + 4 * b + 4 * m;
@@ -1372,9 +1556,14 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
     }
   }
   lds_fence();
+  ME_BSTAMP(3);
 
   // 3. seeds: lane = (block, block row); e = the block's smallest entry with
-  // its chunk and group appended.
+  // its chunk and group appended.  The first read of the staged window: in the
+  // chain kernel (a launch with planes: no step 1) its DMA may still have been
+  // in flight under step 2 (flow_fill).
+  if constexpr (CHAIN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  ME_BSTAMP(7);
   {
     uint32_t e = ~0u;
     for (int lc = lc0; lc < lc1; lc++) {
@@ -1417,6 +1606,7 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
     }
   }
   lds_fence();
+  ME_BSTAMP(4);
 
   // 4. the live list (the planes are dead: the list overlays them)
   int L = 0;
@@ -1459,6 +1649,10 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
       atomicAdd(&ctl->stats[3], 1u);
     }
   }
+  ME_BSTAMP(5);
+#ifdef ME_STAMPS
+  if (bs) bs[6]++;
+#endif
 }
 
 // ------------------------------------------------ flow: the row-split wave-task
@@ -1545,397 +1739,60 @@ __device__ __forceinline__ void flow_split_task(const SearchArgs& p, const QsadG
   }
 }
 
-template <int B, int K, int PC>
-__global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g, FlowJobs jb) {
-  static_assert(B == 16, "cur-block DMA layout of stage_item_wave");
-  constexpr int CW = B / 4;
-  extern __shared__ __align__(16) uint8_t smem[];
-  // Pruning (flow_bound above) is compiled into the 144-byte-pitch instance
-  // only: the planner turns it on for no other shape.
-  const bool prune = PC == 144 && g.prune != 0;
-  // (a pruning launch with box-sum planes: the slim bound scratch, more slots)
-  const bool slim = prune && jb.planes != nullptr;
-  const int NB = !prune ? g.flow_slots : slim ? g.slim_slots : g.prune_slots;
-  const int slot_bytes = g.tile_bytes + g.tb * B * B + (!prune ? 0 : slim ? FLOW_SLIM_BYTES : FLOW_PRUNE_BYTES);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(smem + NB * slot_bytes);  // [NB][tb]
-  FlowCtl* ctl = reinterpret_cast<FlowCtl*>(smem + NB * slot_bytes + NB * g.tb * 8);
-  const int tid = (int)threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int S = p.range;
-
-  // This workgroup's tiles: the XCD band of bid % 8 (a speed heuristic only),
-  // member m takes tiles band0 + m, + n_x, ... (every job's tiles, job-major)
-  const int ntiles = jb.tile_pre[jb.n];
-  const int nwg = (int)gridDim.x, bid = (int)blockIdx.x;
-  const int ng = nwg < 8 ? nwg : 8;
-  const int x = bid % ng, m = bid / ng;
-  const int n_x = nwg / ng + (x < nwg % ng ? 1 : 0);
-  const int band0 = (int)((long)ntiles * x / ng), band1 = (int)((long)ntiles * (x + 1) / ng);
-  const int nitems = band1 - band0 > m ? (band1 - band0 - m + n_x - 1) / n_x : 0;
-  auto tile_of = [&](int k) { return band0 + m + k * n_x; };
-
-  if (tid < 64) {
-    if (tid == 0) ctl->next = 0;
-    if (tid < 16) {
-      ctl->ready[tid] = 0;
-      ctl->done[tid] = 0;
-      if (prune) ctl->live[tid] = 0;
-    }
-    if (prune && tid >= 32 && tid < 36) ctl->stats[tid - 32] = 0;
-    if (prune && tid >= 36 && tid < 39) ctl->split[tid - 36] = 0;
-    if (tid == 16) {
-      ctl->run = 0;
-      ctl->pflags = !prune ? 0u
-                           : (uint32_t)(PF_ON | (g.prune == 2 ? PF_VERIFY : 0) | (g.prune_bypass ? PF_BYPASS : 0) |
-                                        (g.prune_stats ? PF_STATS : 0) | (jb.planes ? PF_PLANES : 0) |
-                                        (g.prune_split ? PF_SPLIT : 0));
-    }
-  }
-  for (int i = tid; i < NB * g.tb; i += (int)blockDim.x) keys[i] = ~0ull;
-  __syncthreads();
-  // wave w < NB stages item w and publishes it
-  if (wave < NB && wave < nitems) {
-    // Staggered start (wave w waits w x 640 cycles): item 0's DMA gets the
-    // CU's memory pipeline first and lands early instead of every item
-    // landing together at the end of one burst (1080p, same box:
-    // 78.4 -> 78.0 us; with the compile-time pitch 79.0 -> 77.3,
-    // profiles/r02ae_ab_flow_start.txt).
-    for (int i = 0; i < wave; i++) __builtin_amdgcn_s_sleep(10);
-    if (g.prio) __builtin_amdgcn_s_setprio(3);  // see me_fast_kernel
-    const Item it0 = flow_item<B, K>(p, g, jb, tile_of(wave), -1);
-    stage_item_wave<B>(p, g, it0, smem + wave * slot_bytes, jb);
-    if constexpr (PC == 144) {
-      // (the bound's first plane rows: issued here, landed by the same wait)
-      FlowPlaneRegs R;
-      const bool pl0 = prune && flow_plane_wanted<B>(it0, ctl);
-      if (pl0) flow_plane_fetch<B, K>(it0, jb, R);
-      else flow_plane_zero(R);
-      if (g.prio) __builtin_amdgcn_s_setprio(0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (prune)
-        flow_bound<B, K>(p, g, it0, smem + wave * slot_bytes, keys + wave * g.tb, ctl, wave, jb, R, pl0);
-    } else {
-      if (g.prio) __builtin_amdgcn_s_setprio(0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    if (lane == 0)
-      __hip_atomic_store(&ctl->ready[wave], (uint32_t)wave + 1u, __ATOMIC_RELEASE,
-                         __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-
-  int kc = 0, basec = 0, lc0c = 0, nwc = 0;  // this wave's view: item kc's first task, task count
-  Item itc;
-  bool have = false;
-#ifdef ME_STAMPS
-  // diagnostic build: per wave [start, first task, loop exit, spin cycles, tasks,
-  // realtime start, realtime end, hw_id | ring slots << 32] (tools/flow_stamps.py)
-  const int fw = bid * 16 + wave;
-  unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_first = 0, st_spin = 0, st_n = 0;
-  const unsigned long long st_r0 = __builtin_amdgcn_s_memrealtime();
-  unsigned long long st_dma = 0, st_bound = 0, st_nb = 0;  // refills: DMA wait, bound phase, count
-  // executed wave-tasks run with 1, 2, 4 lanes per list entry: count << 40 | cycles (list read to key merge)
-  unsigned long long st_k1 = 0, st_k2 = 0, st_k4 = 0;
-  // the tile -> item decode (flow_item) at the advance and at the refill: count << 40 | cycles
-  unsigned long long st_da = 0, st_dr = 0;
-#define ME_DECODE_T0 const unsigned long long st_i0 = __builtin_amdgcn_s_memtime()
-#define ME_DECODE_T1(acc, item)                                                   \
-  do {                                                                            \
-    asm volatile("" ::"s"((item).j), "s"((item).by), "s"((item).bx0));            \
-    (acc) += (1ull << 40) + (__builtin_amdgcn_s_memtime() - st_i0);               \
-  } while (0)
-#else
-#define ME_DECODE_T0
-#define ME_DECODE_T1(acc, item)
-#endif
-  for (;;) {
-    const int pfl = PC == 144 ? __builtin_amdgcn_readfirstlane((int)ctl->pflags) : 0;
-    uint32_t q = 0;
-    if (lane == 0) q = __hip_atomic_fetch_add(&ctl->next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
-    // advance to the item holding task q (pulls are in order: kc only grows)
-    if (!have && kc < nitems) {
-      ME_DECODE_T0;
-      itc = flow_item<B, K>(p, g, jb, tile_of(kc), -1);
-      ME_DECODE_T1(st_da, itc);
-      nwc = flow_tasks<B, K>(p, g, itc, &lc0c);
-      have = true;
-    }
-    while (kc < nitems && (int)q >= basec + nwc) {
-      basec += nwc;
-      kc++;
-      if (kc < nitems) {
-        ME_DECODE_T0;
-        itc = flow_item<B, K>(p, g, jb, tile_of(kc), itc.j);  // (kc grew: its job did not fall)
-        ME_DECODE_T1(st_da, itc);
-        nwc = flow_tasks<B, K>(p, g, itc, &lc0c);
-      }
-    }
-    if (kc >= nitems) break;
-    if (g.fair) __builtin_amdgcn_s_setprio(0);
-    const int slot = kc % NB;
-    // Bounded wait (the ordering argument above says it ends; the bound keeps a
-    // broken invariant from hanging the GPU).  An expired wait is reported:
-    // sched[SCHED_ERR] is set, and the host turns it into ME_EDEVICE
-    // (device_status after the synchronous entry points, me_device_check).
-    int spins = 0;
-#ifdef ME_STAMPS
-    const unsigned long long st_w0 = __builtin_amdgcn_s_memtime();
-#endif
-    while (__hip_atomic_load(&ctl->ready[slot], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) !=
-               (uint32_t)kc + 1u &&
-           ++spins < (1 << 20))
-      __builtin_amdgcn_s_sleep(2);
-    if (spins >= (1 << 20)) {
-      if (lane == 0 && p.sched)
-        __hip_atomic_store(p.sched + SCHED_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      break;
-    }
-#ifdef ME_STAMPS
-    {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      st_spin += now - st_w0;
-      if (!st_first) st_first = now;
-      st_n++;
-    }
-#endif
-    const Item& it = itc;
-    uint8_t* buf = smem + slot * slot_bytes;
-    const uint32_t* cur_lds = reinterpret_cast<const uint32_t*>(buf + g.tile_bytes);
-    const uint32_t tile_off = (uint32_t)(slot * slot_bytes);
-    const int G = g.groups;
-    const int t = (int)q - basec;
-    const int dymin = max(-S, -it.tly), dymax = min(S, p.height - it.h - it.tly);
-    const int lc1 = min(it.nch, (dymax + S) / K + 1);
-    const int valid_lanes = (lc1 - lc0c) * it.nb * G;
-    // Pruning: task t takes the item's live lane-tasks [64 t, 64 t + 64) of the
-    // slot's list; a task past the list only counts itself done.
-    const int nlive = pfl ? __builtin_amdgcn_readfirstlane((int)ctl->live[slot]) : valid_lanes;
-    if (64 * t < nlive) {
-    // Fairness: the SIMD arbiter issues the oldest waves first, so a young
-    // wave's wave-task lags while older waves run through later items (single
-    // 1080p frames: per SIMD one wave ran ~6 wave-tasks, two ran 1 each), and
-    // the slot refill that waits for it stalls every wave behind the ring.
-    // Every 4 rows the wave compares its task with the pull counter and raises
-    // its priority once lo / hi later tasks have been pulled (g.fair; back to
-    // 0 at its next pull).  Only in launches with refills: without them (a
-    // single 1080p frame, every tile staged at the start) the oldest-first
-    // order ends the launch sooner (70.4 vs 74.7 us with the check on,
-    // profiles/r03ad_*).  Tuning build, g.fair bits 16-17 (ME_FAIR): 2 = only
-    // on items whose slot still gets a refill, 3 = on every item.
-    const int fmode = g.fair >> 16;
-    const bool fair = g.fair != 0 && (fmode == 3 || (fmode == 2 ? kc + NB < nitems : nitems > NB));
-    // pull-counter values that raise the priority (two SGPRs across the rows)
-    const int lim1 = __builtin_amdgcn_readfirstlane(fair ? (int)q + (g.fair & 255) : 0x7FFFFFFF);
-    const int lim2 = __builtin_amdgcn_readfirstlane(fair ? (int)q + ((g.fair >> 8) & 255) : 0x7FFFFFFF);
-    // The compare and s_setprio sit in one asm block: as C branches they split
-    // the unrolled row loop into basic blocks, and it spilled 41 VGPRs.
-    auto lag_check = [lim1, lim2, ctl]() {
-      const int nx = __builtin_amdgcn_readfirstlane(
-          (int)__hip_atomic_load(&ctl->next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-      asm volatile(
-          "s_cmp_ge_i32 %0, %2\n\t"
-          "s_cbranch_scc0 1f\n\t"
-          "s_setprio 2\n\t"
-          "s_branch 2f\n"
-          "1:\n\t"
-          "s_cmp_ge_i32 %0, %1\n\t"
-          "s_cbranch_scc0 2f\n\t"
-          "s_setprio 1\n"
-          "2:" ::"s"(nx), "s"(lim1), "s"(lim2) : "scc");
-    };
-    // The task's class: 0 runs whole (below), 1 / 2 split by rows over 2 / 4
-    // lanes per list entry (flow_split_task; pruned h = B items only: an
-    // h = B/2 item's list is full).
-    int cls = 0;
-#ifdef ME_STAMPS
-    const unsigned long long st_k0 = __builtin_amdgcn_s_memtime();
-#endif
-    if constexpr (PC == 144) {
-      const int n = nlive - 64 * t;
-      if ((pfl & PF_SPLIT) && it.h == B && n <= 32) cls = flow_split_parts(n) >> 1;
-      if ((pfl & PF_STATS) && lane == 0) atomicAdd(&ctl->split[cls], 1u);
-      if (cls == 2)
-        flow_split_task<B, K, PC, 4>(p, g, it, smem, buf, tile_off, keys + slot * g.tb, t, n, lc0c, pfl, lag_check);
-      else if (cls == 1)
-        flow_split_task<B, K, PC, 2>(p, g, it, smem, buf, tile_off, keys + slot * g.tb, t, n, lc0c, pfl, lag_check);
-    }
-    if (cls == 0) {
-    const bool live = 64 * t + lane < nlive;
-    const uint16_t* llist = reinterpret_cast<const uint16_t*>(buf + g.tile_bytes + g.tb * B * B);
-    const int i = pfl && live ? (int)llist[64 * t + lane] : 64 * t + lane;
-    const int ii = live ? i : 0;
-    const int bg = (int)__umulhi((uint32_t)ii, g.magic_groups);  // ii / G
-    const int gi = ii - bg * G;
-    const uint32_t magic_nb = 0xFFFFFFFFu / (uint32_t)it.nb + 1u;
-    const int lcr = it.nb == 1 ? bg : (int)__umulhi((uint32_t)bg, magic_nb);
-    const int b = bg - lcr * it.nb;
-    const int lc = lc0c + lcr;
-    const int d0 = lc * K;
-    const int tlx = (it.bx0 + b) * B;
-    uint32_t c[B][CW];
-#pragma unroll
-    for (int y = 0; y < B; y++) {
-      if constexpr (CW == 4) {
-        const uint4 v = reinterpret_cast<const uint4*>(cur_lds)[b * B + y];
-        c[y][0] = v.x; c[y][1] = v.y; c[y][2] = v.z; c[y][3] = v.w;
-      } else {
-        const uint2 v = reinterpret_cast<const uint2*>(cur_lds)[b * B + y];
-        c[y][0] = v.x; c[y][1] = v.y;
-      }
-    }
-    const int dxmin = max(-S, -tlx), dxmax = min(S, p.width - B - tlx);
-    const int jlo = dymin + S - d0, jhi = dymax + S - d0;
-    const bool full_rows = dymin + S <= 0 && dymax + S >= it.nch * K - 1;
-    const int w0 = (b * B) / 4 + gi;
-    uint64_t acc[K];
-    const int jt = gi < K ? gi : K - 1;
-    const uint32_t toff = tile_off + (uint32_t)((lc * K + jt) * g.pitch + b * B + 2 * S);
-    uint32_t tsad = 0;
-    if (it.h == B) {
-      qsad_lane<B, K, B, PC, 4>(smem, g.pitch, tile_off, lc * K, w0, c, acc, lag_check);
-      if (g.fold) tsad = tail_sad<B, B>(smem, g.pitch, toff, c);
-    } else {
-      qsad_lane<B, K, B / 2, PC, 4>(smem, g.pitch, tile_off, lc * K, w0, c, acc, lag_check);
-      if (g.fold) tsad = tail_sad<B, B / 2>(smem, g.pitch, toff, c);
-    }
-    const int dxg = 4 * gi - S - it.a;
-    const bool edge = dxg < dxmin || dxg + 3 > dxmax || !live;
-    uint32_t best;
-    if (full_rows && __builtin_amdgcn_ballot_w64(edge) == 0) {
-      best = lane_best<K, false>(acc, 0u, 0u, jlo, jhi);
-    } else {
-      uint32_t mlo = 0, mhi = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int dx = dxg + k;
-        const uint32_t msk = (dx < dxmin || dx > dxmax) ? 0xFFFFu : 0u;
-        if (k < 2) mlo |= msk << (16 * k);
-        else mhi |= msk << (16 * (k - 2));
-      }
-      best = lane_best<K, true>(acc, mlo, mhi, jlo, jhi);
-    }
-    if (g.fold) {
-      const bool tv = gi < K && jt >= jlo && jt <= jhi && S <= dxmax;
-      best = min(best, tv ? (tsad << 16) | (uint32_t)(5 * jt + 4) : ~0u);
-    }
-    if (live && best < 0xFFFF0000u) {
-      const int idx = (int)(best & 0xFFFFu), jj = idx / 5, k5 = idx - 5 * jj;
-      const int dy = d0 + jj - S, dx = k5 == 4 ? S : 4 * gi + k5 - S - it.a;
-      atomicMin(reinterpret_cast<unsigned long long*>(&keys[slot * g.tb + b]),
-                (unsigned long long)make_key(best >> 16, dx, dy));
-    }
-    if constexpr (PC == 144) {
-      // Verify mode: a lane-task the bound marked dead must hold no candidate
-      // with SAD <= its block's U_b.
-      if ((pfl & PF_VERIFY) && live && best < 0xFFFF0000u) {
-        const uint8_t* pv = buf + g.tile_bytes + g.tb * B * B;
-        if (pv[FLOW_PRUNE_DEAD + i] && (best >> 16) <= reinterpret_cast<const uint32_t*>(pv + FLOW_PRUNE_UB)[b] && p.sched)
-          __hip_atomic_store(p.sched + SCHED_ERR, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    }
-#ifdef ME_STAMPS
-    {  // executed wave-tasks per class: count << 40 | cycles
-      const unsigned long long dt = (1ull << 40) + (__builtin_amdgcn_s_memtime() - st_k0);
-      st_k1 += cls == 0 ? dt : 0;
-      st_k2 += cls == 1 ? dt : 0;
-      st_k4 += cls == 2 ? dt : 0;
-    }
-#endif
-    }
-    // this wave-task is done; the last one of the item writes and refills the slot
-    uint32_t prev = 0;
-    if (lane == 0)
-      prev = __hip_atomic_fetch_add(&ctl->done[slot], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-    prev = (uint32_t)__builtin_amdgcn_readfirstlane((int)prev);
-    if ((int)prev + 1 == nwc) {
-      if (lane < it.nb) {
-        const uint64_t kk = keys[slot * g.tb + lane];
-        uint64_t none = ~0ull;  // materialised here, not kept live (it spilled)
-        asm volatile("" : "+v"(none));
-        keys[slot * g.tb + lane] = none;
-        const int out = (it.by - jb.r0[it.j]) * p.nbx + it.bx0 + lane;
-        int16_t* mv = jb.mv[it.j];
-        store_mv(mv, out, kk);
-        if (jb.cost[it.j]) jb.cost[it.j][out] = (uint32_t)(kk >> 32);
-      }
-      if (lane == 0) __hip_atomic_store(&ctl->done[slot], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const int kn = kc + NB;
-      if (kn < nitems) {
-        if (g.prio) __builtin_amdgcn_s_setprio(3);
-        ME_DECODE_T0;
-        const Item itn = flow_item<B, K>(p, g, jb, tile_of(kn), it.j);  // (kn > kc)
-        ME_DECODE_T1(st_dr, itn);
-#ifdef ME_STAMPS
-        const unsigned long long st_d0 = __builtin_amdgcn_s_memtime();
-#endif
-        stage_item_wave<B>(p, g, itn, buf, jb);
-        if constexpr (PC == 144) {
-          FlowPlaneRegs R;
-          const bool pln = pfl && flow_plane_wanted<B>(itn, ctl);
-          if (pln) flow_plane_fetch<B, K>(itn, jb, R);
-          else flow_plane_zero(R);
-          if (g.prio) __builtin_amdgcn_s_setprio(0);
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef ME_STAMPS
-          const unsigned long long st_d1 = __builtin_amdgcn_s_memtime();
-          st_dma += st_d1 - st_d0;
-          st_bound -= st_d1;
-#endif
-          // (at raised issue priority: nothing of the item runs before its bound ends)
-          if (pfl) {
-            __builtin_amdgcn_s_setprio(3);
-            flow_bound<B, K>(p, g, itn, buf, keys + slot * g.tb, ctl, slot, jb, R, pln);
-            __builtin_amdgcn_s_setprio(0);
-          }
-        } else {
-          if (g.prio) __builtin_amdgcn_s_setprio(0);
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef ME_STAMPS
-          const unsigned long long st_d1 = __builtin_amdgcn_s_memtime();
-          st_dma += st_d1 - st_d0;
-          st_bound -= st_d1;
-#endif
-        }
-#ifdef ME_STAMPS
-        st_bound += __builtin_amdgcn_s_memtime();
-        st_nb++;
-#endif
-        if (lane == 0)
-          __hip_atomic_store(&ctl->ready[slot], (uint32_t)kn + 1u, __ATOMIC_RELEASE,
-                             __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-    }
-  }
-  if constexpr (PC == 144) {
-    // Tuning build: this workgroup's counts, once every wave is out of the loop.
-    if ((__builtin_amdgcn_readfirstlane((int)ctl->pflags) & PF_STATS) && p.sched) {
-      __syncthreads();
-      if (tid < 4) atomicAdd(p.sched + SCHED_PRUNE + tid, ctl->stats[tid]);
-      if (tid >= 4 && tid < 7) atomicAdd(p.sched + SCHED_SPLIT + tid - 4, ctl->split[tid - 4]);
-    }
+// ------------------------------------------------------- flow: filling a slot
+// One wave stages item `it` into the slot at buf and, in a pruning launch
+// (pfl != 0), runs its bound; the caller publishes the slot.  In a launch with
+// box-sum planes the bound needs the cur blocks and its plane registers at
+// once but the window only in its step 3, so those are issued FIRST and the
+// window's DMA last: VMEM loads return in order, and vmcnt(FLOW_WIN_STEPS)
+// behind exactly that many window instructions waits for all that was issued
+// in front of them and for none of them.  The window lands under the bound's
+// steps 1 and 2; flow_bound waits for it in front of step 3, and the
+// vmcnt(0) behind the bound covers the paths that return before step 3 (an
+// h = B/2 item, the bypass state).  Any other launch, and one whose windows
+// (rows_alloc rows, every item's) are not FLOW_WIN_STEPS instructions long,
+// waits for everything as before (PF_EARLY is set at the kernel's start).
+constexpr int FLOW_WIN_STEPS = 12;
+static_assert((5 * 13 + 16 - 1) * 144 > (FLOW_WIN_STEPS - 1) * 1024 && (5 * 13 + 16 - 1) * 144 <= FLOW_WIN_STEPS * 1024,
+              "80 rows x 144 bytes in 1,024-byte DMA steps");
+template <int B, int K>
+__device__ __forceinline__ void flow_fill(const SearchArgs& p, const QsadGeom& g, const Item& it, uint8_t* buf,
+                                          uint64_t* keys, FlowCtl* ctl, int slot, const FlowJobs& jb, int pfl,
+                                          bool boost, unsigned long long* st_landed,
+                                          unsigned long long* bs = nullptr) {
+  FlowPlaneRegs R;
+  const bool pl = pfl && flow_plane_wanted<B>(it, ctl);
+  stage_item_part<B, FLOW_STAGE_CUR>(p, g, it, buf, jb);
+  // (the bound's first plane rows: issued here, landed by the same wait)
+  if (pl) flow_plane_fetch<B, K, true>(it, jb, R);
+  else flow_plane_zero(R);
+  if (pfl & PF_EARLY) {
+    stage_item_part<B, FLOW_STAGE_WIN, FLOW_WIN_STEPS>(p, g, it, buf, jb);
+    if (g.prio) __builtin_amdgcn_s_setprio(0);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(FLOW_WIN_STEPS) : "memory");
+  } else {
+    stage_item_part<B, FLOW_STAGE_WIN>(p, g, it, buf, jb);
+    if (g.prio) __builtin_amdgcn_s_setprio(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
 #ifdef ME_STAMPS
-  if (lane == 0 && fw < (1 << 16)) {
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    unsigned long long* o = g_stamps + 8 * fw;
-    o[0] = st_t0; o[1] = st_first; o[2] = __builtin_amdgcn_s_memtime(); o[3] = st_spin;
-    o[4] = st_n; o[5] = st_r0; o[6] = __builtin_amdgcn_s_memrealtime();
-    o[7] = hw | (unsigned long long)NB << 32;  // (the launch's ring slots above the hw id)
-    // per wave, refills: [DMA wait cycles, bound cycles, refills]; executed
-    // wave-tasks by class: [whole, 2, 4 lanes per entry] as count << 40 | cycles;
-    // flow_item decodes at [the advance, the refill] likewise
-    if (fw < (1 << 14)) {
-      g_wstamps[8 * fw] = st_dma; g_wstamps[8 * fw + 1] = st_bound; g_wstamps[8 * fw + 2] = st_nb;
-      g_wstamps[8 * fw + 3] = st_k1; g_wstamps[8 * fw + 4] = st_k2; g_wstamps[8 * fw + 5] = st_k4;
-      g_wstamps[8 * fw + 6] = st_da; g_wstamps[8 * fw + 7] = st_dr;
-    }
-  }
+  if (st_landed) *st_landed = __builtin_amdgcn_s_memtime();
 #endif
-#undef ME_DECODE_T0
-#undef ME_DECODE_T1
+  if (pfl) {
+    // (a refill at raised issue priority: nothing of the item runs before its bound ends)
+    if (boost) __builtin_amdgcn_s_setprio(3);
+    flow_bound<B, K, true>(p, g, it, buf, keys, ctl, slot, jb, R, pl, bs);
+    if (boost) __builtin_amdgcn_s_setprio(0);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
+
+#define ME_FLOW_CHAIN 0
+#include "me_flow_kernel.inc"
+#undef ME_FLOW_CHAIN
+#define ME_FLOW_CHAIN 1
+#include "me_flow_kernel.inc"
+#undef ME_FLOW_CHAIN
 
 // ------------------------------------------------- flow: the box-sum prepass
 // q = (4x4 box sum) >> 4 of every job's resident reference rows, once per
@@ -2182,6 +2039,11 @@ static FlowJobs job_table(const SearchArgs& p, int wg_per_row, const SearchJob* 
   return jb;
 }
 
+// The item-table entries of the process's last flow launch with planes (-1:
+// none yet); the tuning build's me_debug_flow_table reads it.
+static std::atomic<int> g_last_flow_table{-1};
+int last_flow_table() { return g_last_flow_table.load(std::memory_order_relaxed); }
+
 // One flow-kernel launch over jobs [0, n) (full-height rows and h = B/2
 // bottom rows only; n <= MAX_JOBS).
 static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const SearchJob* jobs, int n,
@@ -2215,15 +2077,32 @@ static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const Sear
       if (e != hipSuccess) return e;
     }
   }
+  // The launch with planes keeps its workgroups' item tables behind the slim
+  // layout where the longest of them fits what the ring leaves of the LDS.
+  int table = 0, table_bytes = 0;
+  if (jb.planes && tuning().flow_table != 0) {
+    int max_by = 0;
+    for (int i = 0; i < n; i++)
+      if (jobs[i].r1 > jobs[i].r0 && jobs[i].r1 - 1 > max_by) max_by = jobs[i].r1 - 1;
+    table = flow_table_entries(g, ntiles, nwg, max_by, FLOW_LDS_BUDGET - g.slim_lds, tuning().flow_table_cap);
+    table_bytes = table * FLOW_ENTRY_BYTES;
+  }
+  if (jb.planes) g_last_flow_table.store(table, std::memory_order_relaxed);
   // 144: the pitch of the 4-block tiles 1080p +-32 gets (row addresses in
   // the ds_read2 offsets); any other pitch takes the runtime-pitch body
 #define ME_FLOW_CASE(PP)                                                                        \
   if (PP == 0 || g.pitch == PP) {                                                               \
-    const int lds = !(PP == 144 && g.prune) ? g.lds : jb.planes ? g.slim_lds : g.prune_lds;     \
-    const hipError_t e = lds_attr((const void*)me_flow_kernel<16, 13, PP>, lds);                \
+    const int lds = !(PP == 144 && g.prune) ? g.lds : jb.planes ? g.slim_lds + table_bytes : g.prune_lds; \
+    const void* fn = PP == 144 && g.prune && jb.planes ? (const void*)me_flow_chain_kernel<16, 13> \
+                                                       : (const void*)me_flow_kernel<16, 13, PP>; \
+    const hipError_t e = lds_attr(fn, lds);                                                     \
     if (e != hipSuccess) return e;                                                              \
-    hipLaunchKernelGGL((me_flow_kernel<16, 13, PP>), dim3((unsigned)nwg), dim3(1024), lds,      \
-                       stream, p, g, jb);                                                       \
+    if (PP == 144 && g.prune && jb.planes)                                                      \
+      hipLaunchKernelGGL((me_flow_chain_kernel<16, 13>), dim3((unsigned)nwg), dim3(1024), lds,  \
+                         stream, p, g, jb, table);                                              \
+    else                                                                                        \
+      hipLaunchKernelGGL((me_flow_kernel<16, 13, PP>), dim3((unsigned)nwg), dim3(1024), lds,    \
+                         stream, p, g, jb);                                                     \
     return hipGetLastError();                                                                   \
   }
   ME_FLOW_CASE(144) ME_FLOW_CASE(0)
@@ -2301,6 +2180,11 @@ hipError_t launch_jobs(const SearchArgs& base, const SearchJob* jobs, int n, hip
 extern "C" int me_debug_wave_stamps(unsigned long long* out, int n_words) {
   if (n_words > (8 << 14)) n_words = 8 << 14;
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(me::g_wstamps), (size_t)n_words * 8, 0,
+                                  hipMemcpyDeviceToHost);
+}
+extern "C" int me_debug_bound_stamps(unsigned long long* out, int n_words) {
+  if (n_words > (16 << 14)) n_words = 16 << 14;
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(me::g_bstamps), (size_t)n_words * 8, 0,
                                   hipMemcpyDeviceToHost);
 }
 extern "C" int me_debug_stamps(unsigned long long* out, int n_words) {

@@ -44,6 +44,9 @@ struct Tuning {
                           // planes of the box-sum prepass (-1 = automatic: flow_planes_on, me_valu_plan.cpp)
   int prune_split = -1;   // ME_PRUNE_SPLIT=0|1: a pruned item's wave-task of <= 32 list entries runs whole / split by dy rows
                           // over 2 or 4 lanes per entry (me_geom.h flow_split_*) (-1 = automatic: on)
+  int flow_table = -1;    // ME_FLOW_TABLE=0|1: the slim launch's workgroups decode their items once into an LDS table
+                          // (me_geom.h FlowEntry) off / on (-1 = automatic: on where the table fits)
+  int flow_table_cap = 0; // ME_FLOW_TABLE_CAP=1..4096: a launch whose longest walk has more items runs without the table
   int prune_stats = 0;    // set by the tuning build: the flow kernel counts live / total lane-tasks and bypassed items
   int flow_one = -1;      // ME_FLOW_ONE=0|1: a batch's flow jobs in launches of one ring / in one launch (-1 = automatic: one)
   int mfma_s2k = -1;      // ME_MFMA_S2K=0|1: 16x16 SSD, S <= 64: S2 from the prepass plane / formed in

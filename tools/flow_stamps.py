@@ -125,6 +125,20 @@ if nref:
     for col, name in ((3, "whole"), (4, "2 lanes/entry"), (5, "4 lanes/entry")):
         cnt, cyc = (ws[:, col] >> 40).sum(), (ws[:, col] & ((1 << 40) - 1)).sum()
         print(f"executed wave-tasks {name}: {cnt}" + (f", mean {cyc / cnt:.0f} cycles" if cnt else ""))
+    # The bound of a refill, split (g_bstamps, cycles per bounded item): cur q
+    # and minlb init, step 2 per chunk, the fold column, step 3 with its wait
+    # for the window DMA apart, step 4.
+    if hasattr(L, "me_debug_bound_stamps"):
+        L.me_debug_bound_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        bbuf = np.zeros(16 << 14, np.uint64)
+        L.me_debug_bound_stamps(bbuf.ctypes.data, bbuf.size)
+        bsp = bbuf.reshape(-1, 16)[:4096].astype(np.int64).sum(axis=0)
+        nbd, nch = max(bsp[6], 1), max(bsp[2], 1)
+        print(f"bound split per bounded item ({bsp[6]} of {nref} refills): init {bsp[0] / nbd:.0f}, step 2 "
+              f"{bsp[1] / nbd:.0f} ({bsp[1] / nch:.0f} per chunk, {bsp[2] / nbd:.2f} chunks), fold column {bsp[3] / nbd:.0f}, "
+              f"window wait {bsp[7] / nbd:.0f}, step 3 {bsp[4] / nbd:.0f}, step 4 {bsp[5] / nbd:.0f}")
+        # the head of the line: a slot's publish to the start of its item's first executed wave-task
+        print(f"publish -> first executed task: mean {bsp[8] / max(bsp[9], 1):.0f} cycles ({bsp[9]} items)")
     # Per XCD: the tile -> item decode (flow_item: the job lookup and the item's
     # geometry) where a wave advances to its next item and where the refill
     # names the item it stages, beside what a refill and a task wait for.
