@@ -82,6 +82,14 @@ static Tuning read_tuning() {
   env_int("ME_PRUNE_SPLIT", 0, 1, &t.prune_split);
   env_int("ME_FLOW_TABLE", 0, 1, &t.flow_table);
   env_int("ME_FLOW_TABLE_CAP", 1, 4096, &t.flow_table_cap);
+  env_int("ME_FLOW_PRE", 0, 1, &t.flow_pre);
+  env_int("ME_FLOW_WGS", 1, 1024, &t.flow_wgs);
+  {
+    int pp = t.flow_pre_prio;
+    env_int("ME_FLOW_PRE_PRIO", 0, 3, &pp);
+    if (pp == 2) fprintf(stderr, "me_hip: ignoring ME_FLOW_PRE_PRIO=2 (0, 1 or 3)\n");
+    else t.flow_pre_prio = pp;
+  }
   t.prune_stats = 1;
   env_int("ME_MFMA_BATCH", 0, 1, &t.mfma_batch);
   env_int("ME_MFMA_S2K", 0, 1, &t.mfma_s2k);
@@ -805,6 +813,22 @@ extern "C" int me_debug_prune_stats(me_ctx* c, uint32_t* out4) {
 // ... the LDS item table of the process's last flow launch with box-sum planes:
 // its entries, 0 if that launch ran without a table, -1 before any such launch.
 extern "C" int me_debug_flow_table(void) { return me::last_flow_table(); }
+// ... the chain kernel's pre-bound since the last call: items pre-bound, items
+// whose post-bound had to wait for it, items that fell back to the whole bound
+// (none where the bypass never engages: every later turn of a slot is pre-bound).
+extern "C" int me_debug_flow_pre_stats(me_ctx* c, uint32_t* out3) {
+  if (!c || c->devs.empty() || !out3) return ME_EINVAL;
+  Dev& d = c->devs[0];
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  int rc = ME_OK;
+  if (hipSetDevice(d.id) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(out3, d.sched + me::SCHED_PRE, 12, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemset(d.sched + me::SCHED_PRE, 0, 12) != hipSuccess)
+    rc = ME_EDEVICE;
+  (void)hipSetDevice(prev);
+  return rc;
+}
 // ... and the executed wave-tasks of pruned launches by split class: run whole
 // (P = 1), with 2 and with 4 lanes per list entry (me_geom.h flow_split_parts).
 extern "C" int me_debug_prune_split_stats(me_ctx* c, uint32_t* out3) {

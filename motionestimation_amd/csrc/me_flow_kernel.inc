@@ -2,21 +2,43 @@
 // me_kernels.hip: ME_FLOW_CHAIN 0 gives me_flow_kernel<B, K, PC> (every launch
 // without box-sum planes: it compiles none of the chain paths), ME_FLOW_CHAIN 1
 // gives me_flow_chain_kernel<B, K> (the item table, flow_fill's early bound, the
-// bound's peeled last chunk).  Two kernels, not one body inlined into two
+// bound's peeled last chunk, one slot fill at the top of the task loop and the
+// pre-bound behind its publish).  Two kernels, not one body inlined into two
 // wrappers: the first must stay the code it was before the chain kernel existed.
 #if ME_FLOW_CHAIN
 // A pruning launch with box-sum planes (jb.planes; the 144-byte pitch).  table:
 // entries of the workgroups' LDS item table behind the control block
 // (flow_table_entries; 0: none, the waves decode their items themselves).
+// pre: bit 0 the pre-bound on (flow_fill), bits 1-2 its issue priority.
+// FlowChainArgs: the arguments as the kernel argument segment lays them out.
+// INVARIANT: its members are me_flow_chain_kernel's parameters, in their order
+// and with their types; the slot fill reads the launch's arguments through it
+// (the task loop's top).  Whoever adds, removes or reorders a parameter edits
+// both; the static_assert below the kernel holds the sizes together.
+struct FlowChainArgs {
+  SearchArgs p;
+  QsadGeom g;
+  FlowJobs jb;
+  int table, pre;
+};
 template <int B, int K>
-__global__ __launch_bounds__(1024) void me_flow_chain_kernel(SearchArgs p, QsadGeom g, FlowJobs jb, int table) {
+__global__ __launch_bounds__(1024) void me_flow_chain_kernel(SearchArgs p, QsadGeom g, FlowJobs jb, int table,
+                                                             int pre) {
+  // (the parameter list above is FlowChainArgs, member for member: see there)
+  static_assert(std::is_same<decltype(p), decltype(FlowChainArgs::p)>::value &&
+                    std::is_same<decltype(g), decltype(FlowChainArgs::g)>::value &&
+                    std::is_same<decltype(jb), decltype(FlowChainArgs::jb)>::value &&
+                    std::is_same<decltype(table), decltype(FlowChainArgs::table)>::value &&
+                    std::is_same<decltype(pre), decltype(FlowChainArgs::pre)>::value &&
+                    offsetof(FlowChainArgs, pre) + sizeof(int) == sizeof(FlowChainArgs),
+                "FlowChainArgs mirrors this kernel's parameters");
   constexpr int PC = 144;
-  constexpr bool CHAIN = true;
+  [[maybe_unused]] constexpr bool CHAIN = true;
 #else
 template <int B, int K, int PC>
 __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g, FlowJobs jb) {
-  constexpr bool CHAIN = false;
-  constexpr int table = 0;
+  [[maybe_unused]] constexpr bool CHAIN = false;
+  [[maybe_unused]] constexpr int table = 0;
 #endif
   static_assert(B == 16, "cur-block DMA layout of stage_item_wave");
   constexpr int CW = B / 4;
@@ -68,6 +90,9 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     }
     if (prune && tid >= 32 && tid < 36) ctl->stats[tid - 32] = 0;
     if (prune && tid >= 36 && tid < 39) ctl->split[tid - 36] = 0;
+#if ME_FLOW_CHAIN
+    if (tid >= 39 && tid < 42) ctl->pre[tid - 39] = 0;
+#endif
     if (tid == 16) {
       ctl->run = 0;
       ctl->pflags = !prune ? 0u
@@ -77,6 +102,7 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
                                         // (every item's window is rows_alloc rows: g.tile_bytes = it.prows * g.pitch,
                                         // the bytes stage_item_wave's steps cover, because cpp == chunks in a flow plan)
                                         (tabled0 ? PF_TABLE : 0) |
+                                        (slim && (pre & 1) ? PF_PRE | ((pre >> 1) & 3) << PF_PRE_PRIO_SHIFT : 0) |
                                         (slim && g.cpp == g.chunks && g.tile_bytes > (FLOW_WIN_STEPS - 1) * 1024 &&
                                                  g.tile_bytes <= FLOW_WIN_STEPS * 1024
                                              ? PF_EARLY
@@ -130,6 +156,17 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
   }
 #endif
   __syncthreads();
+#if ME_FLOW_CHAIN
+  // Wave w < NB stages item w and publishes it, by the one copy of the slot
+  // fill this kernel has: at the top of the task loop, where the wave that ran
+  // an item's last task also arrives with the slot's next item (kfill in slot
+  // sfill).  Staggered as below.
+  int kfill = -1, sfill = 0;
+  if (wave < NB && wave < nitems) {
+    for (int i = 0; i < wave; i++) __builtin_amdgcn_s_sleep(10);
+    kfill = sfill = wave;
+  }
+#else
   // wave w < NB stages item w and publishes it
   if (wave < NB && wave < nitems) {
     // Staggered start (wave w waits w x 640 cycles): item 0's DMA gets the
@@ -139,12 +176,6 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     // profiles/r02ae_ab_flow_start.txt).
     for (int i = 0; i < wave; i++) __builtin_amdgcn_s_sleep(10);
     if (g.prio) __builtin_amdgcn_s_setprio(3);  // see me_fast_kernel
-#if ME_FLOW_CHAIN
-    const Item it0 = tabled0 ? flow_entry_item(p, g, B, K, (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[wave].pack))
-                            : flow_item<B, K>(p, g, jb, tile_of(wave), -1);
-    const int pf0 = __builtin_amdgcn_readfirstlane((int)ctl->pflags);
-    flow_fill<B, K>(p, g, it0, smem + wave * slot_bytes, keys + wave * g.tb, ctl, wave, jb, pf0, false, nullptr);
-#else
     const Item it0 = flow_item<B, K>(p, g, jb, tile_of(wave), -1);
     stage_item_wave<B>(p, g, it0, smem + wave * slot_bytes, jb);
     if constexpr (PC == 144) {
@@ -161,7 +192,6 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       if (g.prio) __builtin_amdgcn_s_setprio(0);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-#endif
 #ifdef ME_STAMPS
     if (lane == 0 && (int)blockIdx.x < (1 << 12)) {
       g_first[(int)blockIdx.x * 16 + wave] = ~0ull;
@@ -172,6 +202,7 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       __hip_atomic_store(&ctl->ready[wave], (uint32_t)wave + 1u, __ATOMIC_RELEASE,
                          __HIP_MEMORY_SCOPE_WORKGROUP);
   }
+#endif
 
   int kc = 0, basec = 0, lc0c = 0, nwc = 0;  // this wave's view: item kc's first task, task count
   Item itc;
@@ -188,7 +219,10 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
   // the tile -> item decode (flow_item) at the advance and at the refill: count << 40 | cycles
   unsigned long long st_da = 0, st_dr = 0;
   unsigned long long st_pt = 0, st_pn = 0;  // publish -> first executed task: cycles, items
-  unsigned long long st_b[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the bound's split (g_bstamps)
+  // the bound's split (g_bstamps); [8], [9]: the chain kernel's post-bounds' waits on BUSY, cycles and count
+  unsigned long long st_b[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // the chain kernel: pre-bounds (cycles, count), last task done -> publish of the refills (cycles; st_nb counts them)
+  unsigned long long st_pre = 0, st_pren = 0, st_rp = 0, st_last = 0;
 #define ME_DECODE_T0 const unsigned long long st_i0 = __builtin_amdgcn_s_memtime()
 #define ME_DECODE_T1(acc, item)                                                   \
   do {                                                                            \
@@ -201,6 +235,91 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
 #endif
   for (;;) {
     const int pfl = PC == 144 ? __builtin_amdgcn_readfirstlane((int)ctl->pflags) : 0;
+#if ME_FLOW_CHAIN
+    if (kfill >= 0) {
+      // Fill slot sfill with item kfill and publish it; then the pre-bound of
+      // the slot's next item (flow_fill's comment has the marker's protocol).
+      const int kn = kfill, slotn = sfill;
+      // The fill reads the launch's arguments through a pointer to the kernel
+      // argument segment that the compiler cannot follow out of the loop: what
+      // it derives from the arguments themselves is all formed in front of the
+      // task loop and held across it, in SGPRs the loop has to spill.
+      typedef const __attribute__((address_space(4))) FlowChainArgs* ArgPtr;
+      ArgPtr ka = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+      asm volatile("" : "+s"(ka));
+      const SearchArgs& pa = *(const SearchArgs*)&ka->p;
+      const QsadGeom& ga = *(const QsadGeom*)&ka->g;
+      const FlowJobs& ja = *(const FlowJobs*)&ka->jb;
+      uint8_t* bufn = smem + slotn * slot_bytes;
+      if (ga.prio) __builtin_amdgcn_s_setprio(3);  // see me_fast_kernel
+      ME_DECODE_T0;
+      // (kn > kc: the job of this wave's current item is not behind kn's)
+      const Item itn = (pfl & PF_TABLE)
+                           ? flow_entry_item(pa, ga, B, K, (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[kn].pack))
+                           : flow_item<B, K>(pa, ga, ja, tile_of(kn), have ? itc.j : -1);
+      ME_DECODE_T1(st_dr, itn);
+      bool expired = false;
+#ifdef ME_STAMPS
+      const unsigned long long st_d0 = __builtin_amdgcn_s_memtime();
+      unsigned long long st_d1 = 0;
+      flow_fill<B, K>(pa, ga, itn, bufn, keys + slotn * ga.tb, ctl, slotn, ja, pfl, kn >= NB, kn, NB, &expired, &st_d1,
+                      kn >= NB ? st_b : nullptr);
+      if (kn >= NB) {
+        st_dma += st_d1 - st_d0;
+        st_bound += __builtin_amdgcn_s_memtime() - st_d1;
+        st_nb++;
+      }
+#else
+      flow_fill<B, K>(pa, ga, itn, bufn, keys + slotn * ga.tb, ctl, slotn, ja, pfl, kn >= NB, kn, NB, &expired, nullptr);
+#endif
+      if (expired) break;
+      // the marker of this turn: whether item kn + NB is pre-bound behind the publish
+      const int kp = kn + NB;
+      bool prb = (pfl & PF_PRE) && kp < nitems;
+      if (prb && (pfl & PF_BYPASS))
+        prb = __builtin_amdgcn_readfirstlane(
+                  (int)__hip_atomic_load(&ctl->run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < 4;
+      Item itp = itn;
+      if (prb) {
+        itp = (pfl & PF_TABLE)
+                  ? flow_entry_item(pa, ga, B, K, (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[kp].pack))
+                  : flow_item<B, K>(pa, ga, ja, tile_of(kp), itn.j);
+        prb = itp.h == B;
+      }
+      uint32_t* mark = flow_mark_of<B>(ga, bufn);
+      if ((pfl & PF_PRE) && lane == 0)
+        __hip_atomic_store(mark, prb ? flow_mark_busy(kp) : FLOW_MARK_NONE, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+#ifdef ME_STAMPS
+      if (lane == 0 && bid < (1 << 12)) {
+        g_first[bid * 16 + slotn] = ~0ull;
+        g_pub[bid * 16 + slotn] = __builtin_amdgcn_s_memtime();
+      }
+      if (kn >= NB) st_rp += __builtin_amdgcn_s_memtime() - st_last;
+#endif
+      if (lane == 0)
+        __hip_atomic_store(&ctl->ready[slotn], (uint32_t)kn + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (prb) {
+#ifdef ME_STAMPS
+        const unsigned long long st_p0 = __builtin_amdgcn_s_memtime();
+#endif
+        // (off the chain unless it is late: the issue priority the launch names)
+        const int pp = (pfl & PF_PRE_PRIO) >> PF_PRE_PRIO_SHIFT;
+        if (pp == 3) __builtin_amdgcn_s_setprio(3);
+        else if (pp == 1) __builtin_amdgcn_s_setprio(1);
+        flow_prebound<B, K>(pa, ga, itp, bufn, keys + slotn * ga.tb, ctl, slotn, ja);
+        __builtin_amdgcn_s_setprio(0);
+        if (lane == 0) {
+          __hip_atomic_store(mark, flow_mark_done(kp), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+          if (pfl & PF_STATS) atomicAdd(&ctl->pre[0], 1u);
+        }
+#ifdef ME_STAMPS
+        st_pre += __builtin_amdgcn_s_memtime() - st_p0;
+        st_pren++;
+#endif
+      }
+    }
+#endif
     uint32_t q = 0;
     if (lane == 0) q = __hip_atomic_fetch_add(&ctl->next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
@@ -423,12 +542,16 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
 #endif
     }
     // this wave-task is done; the last one of the item writes and refills the slot
+#if ME_FLOW_CHAIN
+    kfill = -1;
+#endif
     uint32_t prev = 0;
     if (lane == 0)
       prev = __hip_atomic_fetch_add(&ctl->done[slot], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
     prev = (uint32_t)__builtin_amdgcn_readfirstlane((int)prev);
     if ((int)prev + 1 == nwc) {
 #ifdef ME_STAMPS
+      st_last = __builtin_amdgcn_s_memtime();
       if (bid < (1 << 12)) {  // (every task of the item is done: its earliest start stands)
         const unsigned long long f = __hip_atomic_load(&g_first[bid * 16 + slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long pb = __hip_atomic_load(&g_pub[bid * 16 + slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -450,24 +573,16 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       }
       if (lane == 0) __hip_atomic_store(&ctl->done[slot], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       const int kn = kc + NB;
+#if ME_FLOW_CHAIN
+      // (the slot's next item: filled and published at the top of the loop)
+      if (kn < nitems) {
+        kfill = kn;
+        sfill = slot;
+      }
+#else
       if (kn < nitems) {
         if (g.prio) __builtin_amdgcn_s_setprio(3);
         ME_DECODE_T0;
-#if ME_FLOW_CHAIN
-        const Item itn = tabled ? flow_entry_item(p, g, B, K, (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[kn].pack))
-                                : flow_item<B, K>(p, g, jb, tile_of(kn), it.j);  // (kn > kc)
-        ME_DECODE_T1(st_dr, itn);
-#ifdef ME_STAMPS
-        const unsigned long long st_d0 = __builtin_amdgcn_s_memtime();
-        unsigned long long st_d1 = 0;
-        flow_fill<B, K>(p, g, itn, buf, keys + slot * g.tb, ctl, slot, jb, pfl, true, &st_d1, st_b);
-        st_dma += st_d1 - st_d0;
-        st_bound += __builtin_amdgcn_s_memtime() - st_d1;
-        st_nb++;
-#else
-        flow_fill<B, K>(p, g, itn, buf, keys + slot * g.tb, ctl, slot, jb, pfl, true, nullptr);
-#endif
-#else
         const Item itn = flow_item<B, K>(p, g, jb, tile_of(kn), it.j);  // (kn > kc)
         ME_DECODE_T1(st_dr, itn);
 #ifdef ME_STAMPS
@@ -509,7 +624,6 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
         st_bound += __builtin_amdgcn_s_memtime();
         st_nb++;
 #endif
-#endif
 #ifdef ME_STAMPS
         if (lane == 0 && bid < (1 << 12)) {
           g_first[bid * 16 + slot] = ~0ull;
@@ -520,6 +634,7 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
           __hip_atomic_store(&ctl->ready[slot], (uint32_t)kn + 1u, __ATOMIC_RELEASE,
                              __HIP_MEMORY_SCOPE_WORKGROUP);
       }
+#endif
     }
   }
   if constexpr (PC == 144) {
@@ -528,6 +643,9 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       __syncthreads();
       if (tid < 4) atomicAdd(p.sched + SCHED_PRUNE + tid, ctl->stats[tid]);
       if (tid >= 4 && tid < 7) atomicAdd(p.sched + SCHED_SPLIT + tid - 4, ctl->split[tid - 4]);
+#if ME_FLOW_CHAIN
+      if (tid >= 7 && tid < 10) atomicAdd(p.sched + SCHED_PRE + tid - 7, ctl->pre[tid - 7]);
+#endif
     }
   }
 #ifdef ME_STAMPS
@@ -548,6 +666,9 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
 #pragma unroll
       for (int i = 0; i < 8; i++) g_bstamps[16 * fw + i] = st_b[i];
       g_bstamps[16 * fw + 8] = st_pt; g_bstamps[16 * fw + 9] = st_pn;
+      // the chain kernel: waits on BUSY [cycles, count], pre-bounds [cycles, count], last task done -> publish of the refills
+      g_bstamps[16 * fw + 10] = st_b[8]; g_bstamps[16 * fw + 11] = st_b[9];
+      g_bstamps[16 * fw + 12] = st_pre; g_bstamps[16 * fw + 13] = st_pren; g_bstamps[16 * fw + 14] = st_rp;
     }
   }
 #endif

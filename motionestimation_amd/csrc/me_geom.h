@@ -163,6 +163,15 @@ static_assert(FLOW_PRUNE_UB + 16 <= FLOW_SLIM_MINLB && FLOW_PRUNE_UB + 16 <= FLO
               "list, verify flags and U_b lie in front of minlb in both layouts");
 static_assert(FLOW_SLIM_BYTES == 2368 && FLOW_SLIM_BYTES % 16 == 0 && FLOW_PRUNE_BYTES % 16 == 0,
               "slots stay 16-byte aligned");
+// The chain kernel's pre-bound marker, one word per slot in the free bytes
+// between U_b and minlb of the slim scratch: whether minlb and the cur blocks'
+// box sums of the slot's NEXT item (item + ring slots of the one published in
+// it) are being formed, or stand, while the published item's tasks still run.
+constexpr int FLOW_SLIM_MARK = FLOW_PRUNE_UB + 16;
+static_assert(FLOW_SLIM_MARK >= 976 && FLOW_SLIM_MARK + 4 <= FLOW_SLIM_MINLB, "the marker lies in the gap 976 .. 1023");
+constexpr uint32_t FLOW_MARK_NONE = 0;
+constexpr uint32_t flow_mark_busy(int item) { return 2u * (uint32_t)(item + 1); }
+constexpr uint32_t flow_mark_done(int item) { return 2u * (uint32_t)(item + 1) + 1u; }
 
 // A search job: block rows [r0, r1) of one frame (or row stripe), its planes
 // (ref / cur hold frame rows from ref_row0 / cur_row0, as in SearchArgs) and
@@ -386,6 +395,17 @@ ME_HOST_DEVICE inline uint32_t flow_plane_lane_byte(int pitch, int k, int byte) 
 }
 ME_HOST_DEVICE inline uint32_t flow_plane_byte(int pitch, int rel, int X0, int yp, int k, int byte) {
   return flow_plane_row_byte(pitch, rel, X0, yp) + flow_plane_lane_byte(pitch, k, byte);
+}
+// Byte offset from a job's cur pointer (its rows start at frame row cur_row0)
+// of the r-th (0 .. 3) of the four dwords whose byte sum is the 4x4 box sum
+// lane = block << 4 | sub-block row << 2 | sub-block column of the item at
+// (tly, bx0) owns: the chain kernel's pre-bound forms the cur blocks' q from
+// global memory with them, while the slot's cur area still belongs to the item
+// in front.  The bytes are those the slot's cur DMA brings (stage_item_part:
+// granule d -> row (d >> 4) & 15 of block d >> 8), B = 16.
+ME_HOST_DEVICE inline uint32_t flow_qcur_byte(int cur_row0, int stride, int tly, int bx0, int lane, int r) {
+  const int b = lane >> 4, sy = (lane >> 2) & 3, sx = lane & 3;
+  return (uint32_t)((tly - cur_row0 + 4 * sy + r) * stride + (bx0 + b) * 16 + 4 * sx);
 }
 #undef ME_HOST_DEVICE
 // No such load straddles the end of a phase row, so none straddles the end of

@@ -28,6 +28,10 @@ constexpr int SCHED_PRUNE = 24;
 // ... and its executed wave-tasks run whole, with 2 and with 4 lanes per list
 // entry (the row split, me_geom.h flow_split_parts): three words.
 constexpr int SCHED_SPLIT = 28;
+// ... and the chain kernel's pre-bound (flow_fill): items pre-bound, items whose
+// post-bound met the marker BUSY, items that fell back (bounded items of a slot's
+// second or later turn that found no pre-bound and ran the whole bound): three words.
+constexpr int SCHED_PRE = 20;
 
 // The packed key of a candidate: the unsigned minimum of keys is the smallest
 // cost and, among equal costs, the first displacement in raster order.

@@ -969,6 +969,8 @@ struct FlowCtl {
   uint32_t live[16];   // live lane-tasks of the slot's item (its list's length)
   uint32_t stats[4];   // tuning build: live, all lane-tasks, bypassed items, items (flushed at the end)
   uint32_t split[3];   // tuning build: executed wave-tasks run with 1, 2, 4 lanes per list entry
+  uint32_t pre[3];     // tuning build, chain kernel: items pre-bound, post-bounds that met BUSY, items that fell back (a bounded
+                       // item of a slot's second or later turn whose marker named no pre-bound: it ran the whole bound)
 };
 // PF_PLANES: the launch has box-sum planes (FlowJobs::planes): flow_bound skips
 // its step 1 and loads the plane rows of step 2 from them (the slim scratch).
@@ -976,9 +978,11 @@ struct FlowCtl {
 // (flow_split_task below).
 // PF_TABLE: the workgroup's items are decoded in the LDS item table behind this
 // block (me_geom.h FlowEntry).  PF_EARLY: a slot's fill issues the window DMA
-// last and starts the bound under it (flow_fill below).
+// last and starts the bound under it (flow_fill below).  PF_PRE: the wave that
+// publishes an item forms the bound's minlb of the slot's next item behind the
+// publish (the pre-bound, flow_fill below); PF_PRE_PRIO: its issue priority.
 enum { PF_ON = 1, PF_VERIFY = 2, PF_BYPASS = 4, PF_STATS = 8, PF_PLANES = 16, PF_SPLIT = 32, PF_TABLE = 64,
-       PF_EARLY = 128 };
+       PF_EARLY = 128, PF_PRE = 256, PF_PRE_PRIO_SHIFT = 9, PF_PRE_PRIO = 3 << PF_PRE_PRIO_SHIFT };
 static_assert(sizeof(FlowCtl) <= FLOW_CTL_BYTES, "control block of the pruning launch");
 
 // Tile of the flow kernel's launch -> its item (all dy chunks: one pass).  A
@@ -1225,11 +1229,21 @@ __device__ __forceinline__ void flow_plane_zero(FlowPlaneRegs& R) {
 // R: the item's first plane rows where `fetched` (flow_plane_fetch, issued by
 // the caller in front of its wait for the window); else loaded here if the
 // launch has planes.
-template <int B, int K, bool CHAIN = false>
+// The chain kernel runs the bound in two parts where it can (flow_fill below):
+// PRE: the pre-bound alone, that is the init, step 2 and the fold column of an
+// h = B item of a launch with planes, whose slot still holds the item in front:
+// it reads the cur blocks from global memory (flow_qcur_byte), writes minlb and
+// qcur and nothing else, and takes no part in the bypass accounting.  mark
+// (not PRE): the slot's marker says that this item's pre-bound ran or is
+// running, so the bound waits for its DONE (bounded; *expired) and then runs
+// steps 3 and 4 alone, unless the bypass state gives the item its full list.
+template <int B, int K, bool CHAIN = false, bool PRE = false>
 __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& g, const Item& it,
                                            uint8_t* buf, uint64_t* keys, FlowCtl* ctl, int slot,
                                            const FlowJobs& jb, FlowPlaneRegs& R, bool fetched,
-                                           unsigned long long* bs = nullptr) {
+                                           unsigned long long* bs = nullptr, const uint32_t* mark = nullptr,
+                                           int kitem = 0, bool* expired = nullptr) {
+  static_assert(CHAIN || !PRE, "the pre-bound is the chain kernel's");
   constexpr int S = 32, G = 16, TB = 4, P = 144;
 #ifdef ME_STAMPS
   unsigned long long bt = __builtin_amdgcn_s_memtime();  // (bs: the stamps build's split of a refill's bound)
@@ -1256,7 +1270,7 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
   // compare-and-swap: the bound phases of the other slots keep bypassing).
   int run = 0;
   bool prober = false;
-  if (pf & PF_BYPASS) {
+  if (!PRE && (pf & PF_BYPASS)) {
     run = __builtin_amdgcn_readfirstlane(
         (int)__hip_atomic_load(&ctl->run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
     if (run == 3 && it.h == B) {
@@ -1269,7 +1283,41 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
     }
   }
   const bool bypass = it.h == B && run >= 4;
-  if (it.h != B || bypass) {
+  // The pre-bound of this item, if the marker names it, must have ended before
+  // anything else here: also on the bypass path, which ignores what it left but
+  // publishes the item, and the next pre-bound of the slot writes the same minlb.
+  // (a constant where there is no marker: the kernels without one compile the code they had)
+  std::conditional_t<CHAIN && !PRE, bool, std::false_type> have_pre{};
+  if constexpr (CHAIN && !PRE) {
+    if (mark) {
+#ifdef ME_STAMPS
+      const unsigned long long wt0 = __builtin_amdgcn_s_memtime();
+#endif
+      int spins = 0;
+      while (__hip_atomic_load(mark, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != flow_mark_done(kitem) &&
+             ++spins < (1 << 20))
+        __builtin_amdgcn_s_sleep(2);
+      if (spins >= (1 << 20)) {
+        if (lane == 0 && p.sched)
+          __hip_atomic_store(p.sched + SCHED_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *expired = true;
+        return;
+      }
+#ifdef ME_STAMPS
+      if (bs && spins) {
+        bs[8] += __builtin_amdgcn_s_memtime() - wt0;
+        bs[9]++;
+        bt = __builtin_amdgcn_s_memtime();
+      }
+#endif
+      if (stats && lane == 0 && spins) atomicAdd(&ctl->pre[1], 1u);
+      have_pre = !bypass;
+    } else if (stats && lane == 0 && kitem >= 0 && it.h == B && !bypass) {
+      // fell back: a bounded item of a slot's later turn (kitem >= 0: its marker was written) found no pre-bound
+      atomicAdd(&ctl->pre[2], 1u);
+    }
+  }
+  if (!PRE && (it.h != B || bypass)) {
     for (int r = 0; r < nw; r++) {
       const int idx = 64 * r + lane;
       if (idx < valid_lanes) list[idx] = (uint16_t)idx;
@@ -1293,6 +1341,19 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
   // 1. box sums: the lane owns window columns x0, x0 + 1 and walks the 80 rows
   // with a sliding 4-row sum of the packed horizontal 4-sums.  (Not in a
   // launch with planes: the same bytes wherever a valid candidate reads them.)
+  if (!have_pre) {
+  [[maybe_unused]] uint32_t cg[4];  // PRE: the lane's four cur dwords (issued in front of the plane rows: they return first)
+  if constexpr (PRE) {
+    const __amdgpu_buffer_rsrc_t rcur =
+        __builtin_amdgcn_make_buffer_rsrc((void*)jb.cur[it.j], (short)0, jb.cur_bytes[it.j], 0x00020000);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      // (a block past the tile's last: an offset no descriptor holds, the load returns 0)
+      const uint32_t off = (lane >> 4) < it.nb ? flow_qcur_byte(jb.cur_row0[it.j], p.stride, it.tly, it.bx0, lane, r)
+                                               : 0x80000000u;
+      cg[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rcur, (int)off, 0, 0);
+    }
+  }
   if (planes) {
     if (!fetched) flow_plane_fetch<B, K, CHAIN>(it, jb, R);
   } else {
@@ -1319,24 +1380,30 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
     // q of the cur blocks: lane = (block, sub-block row, sub-block column)
     const uint32_t* cw = cur + ((lane >> 4) * B + 4 * ((lane >> 2) & 3)) * 4 + (lane & 3);
     uint32_t sum = 0;
+    if constexpr (PRE) {
+#pragma unroll
+      for (int r = 0; r < 4; r++) sum = __builtin_amdgcn_sad_u8(cg[r], 0u, sum);
+    } else {
 #pragma unroll
     for (int r = 0; r < 4; r++) sum = __builtin_amdgcn_sad_u8(cw[4 * r], 0u, sum);
+    }
     reinterpret_cast<uint8_t*>(qcur)[lane] = (uint8_t)(sum >> 4);
 #pragma unroll
     for (int r = 0; r < 5; r++) minlb[64 * r + lane] = ~0u;
   }
   lds_fence();
   ME_BSTAMP(0);
+  }
 
   const int b = lane >> 4;
   const int dxmin = max(-S, -(it.bx0 + b) * B), dxmax = min(S, p.width - B - (it.bx0 + b) * B);
   const int Ylo = dymin + S, Yhi = dymax + S;
-  uint32_t qc[4];
-#pragma unroll
-  for (int sy = 0; sy < 4; sy++) qc[sy] = qcur[b * 4 + sy];
   // 2. bounds: lane = (block, x phase k, 4 dx groups 4m..4m+3); u16 t of a qsad
   // is the candidate dx + S = 4 (4m + t) + k.
-  {
+  if (!have_pre) {
+    uint32_t qc[4];
+#pragma unroll
+    for (int sy = 0; sy < 4; sy++) qc[sy] = qcur[b * 4 + sy];
     const int k = (lane >> 2) & 3, m = lane & 3;
     uint32_t mlo = 0, mhi = 0;
 #pragma unroll
@@ -1557,6 +1624,7 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
   }
   lds_fence();
   ME_BSTAMP(3);
+  if constexpr (PRE) return;
 
   // 3. seeds: lane = (block, block row); e = the block's smallest entry with
   // its chunk and group appended.  The first read of the staged window: in the
@@ -1755,13 +1823,58 @@ __device__ __forceinline__ void flow_split_task(const SearchArgs& p, const QsadG
 constexpr int FLOW_WIN_STEPS = 12;
 static_assert((5 * 13 + 16 - 1) * 144 > (FLOW_WIN_STEPS - 1) * 1024 && (5 * 13 + 16 - 1) * 144 <= FLOW_WIN_STEPS * 1024,
               "80 rows x 144 bytes in 1,024-byte DMA steps");
+//
+// The pre-bound (PF_PRE).  Init, step 2 and the fold column of the bound, a
+// third of a slot's item-to-item chain, read only the item's cur bytes, its
+// plane rows and its geometry, and write only minlb and qcur, which are dead
+// in the slot once the item in front has its list.  So the wave that publishes
+// item kn runs them for item kn + NB behind the publish (flow_prebound), while
+// kn's tasks wait for waves and execute, and the slot's marker word tells the
+// wave that later fills the slot with kn + NB what it finds:
+//   writer, about to publish kn:  marker = BUSY(kn + NB) if it will pre-bound
+//     (PF_PRE, kn + NB < nitems, an h = B item, not the bypass state), else
+//     NONE; the ready store (release); the pre-bound; marker = DONE(kn + NB)
+//     (release).
+//   reader, having run kn's last task (so it acquired kn's ready word and sees
+//     the marker of this turn: NONE, BUSY or DONE of kn + NB, never an older
+//     one): on BUSY / DONE of its item it issues no plane fetch, evaluates the
+//     bypass state as ever, waits for DONE (flow_bound) and runs steps 3 and 4;
+//     on anything else it runs the whole bound, the code it always ran.
+// No deadlock: between BUSY and DONE the writer executes straight-line code
+// whose only waits are for its own loads and LDS operations (vmcnt, lgkmcnt),
+// so DONE follows BUSY whatever the other waves do; the reader can see BUSY
+// only after kn's publish, which the writer has behind it; NONE and DONE are
+// final for the turn.  The reader's wait is bounded like the ready wait.  The
+// first NB items have no writer: their slots' marker bytes are whatever the LDS
+// held, and kitem < NB reads none of them.
+// Exactness: minlb is a function of the cur bytes, the plane bytes and the
+// geometry alone, so the list is the one the whole bound builds.
+template <int B>
+__device__ __forceinline__ uint32_t* flow_mark_of(const QsadGeom& g, uint8_t* buf) {
+  return reinterpret_cast<uint32_t*>(buf + g.tile_bytes + g.tb * B * B + FLOW_SLIM_MARK);
+}
+template <int B, int K>
+__device__ __forceinline__ void flow_prebound(const SearchArgs& p, const QsadGeom& g, const Item& it, uint8_t* buf,
+                                              uint64_t* keys, FlowCtl* ctl, int slot, const FlowJobs& jb) {
+  FlowPlaneRegs R;
+  flow_bound<B, K, true, true>(p, g, it, buf, keys, ctl, slot, jb, R, false);
+}
+// kitem: the item's index in the workgroup's walk; *expired: the wait for the
+// item's pre-bound ran out (the error word is set: the caller leaves the task loop).
 template <int B, int K>
 __device__ __forceinline__ void flow_fill(const SearchArgs& p, const QsadGeom& g, const Item& it, uint8_t* buf,
                                           uint64_t* keys, FlowCtl* ctl, int slot, const FlowJobs& jb, int pfl,
-                                          bool boost, unsigned long long* st_landed,
-                                          unsigned long long* bs = nullptr) {
+                                          bool boost, int kitem, int nb_slots, bool* expired,
+                                          unsigned long long* st_landed, unsigned long long* bs = nullptr) {
   FlowPlaneRegs R;
-  const bool pl = pfl && flow_plane_wanted<B>(it, ctl);
+  const uint32_t* mark = nullptr;
+  if ((pfl & PF_PRE) && kitem >= nb_slots) {
+    const uint32_t* mk = flow_mark_of<B>(g, buf);
+    const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)__hip_atomic_load(mk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    if ((v >> 1) == (uint32_t)kitem + 1u) mark = mk;
+  }
+  const bool pl = pfl && !mark && flow_plane_wanted<B>(it, ctl);
   stage_item_part<B, FLOW_STAGE_CUR>(p, g, it, buf, jb);
   // (the bound's first plane rows: issued here, landed by the same wait)
   if (pl) flow_plane_fetch<B, K, true>(it, jb, R);
@@ -1781,7 +1894,9 @@ __device__ __forceinline__ void flow_fill(const SearchArgs& p, const QsadGeom& g
   if (pfl) {
     // (a refill at raised issue priority: nothing of the item runs before its bound ends)
     if (boost) __builtin_amdgcn_s_setprio(3);
-    flow_bound<B, K, true>(p, g, it, buf, keys, ctl, slot, jb, R, pl, bs);
+    // (kitem to the bound: -1 where the slot's marker is not this launch's, the first ring turn or no PF_PRE)
+    flow_bound<B, K, true>(p, g, it, buf, keys, ctl, slot, jb, R, pl, bs, mark,
+                           (pfl & PF_PRE) && kitem >= nb_slots ? kitem : -1, expired);
     if (boost) __builtin_amdgcn_s_setprio(0);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2051,7 +2166,9 @@ static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const Sear
   FlowJobs jb = job_table(p, g.wg_per_row, jobs, n);
   const int ntiles = jb.tile_pre[jb.n];
   if (ntiles <= 0) return hipSuccess;
-  const int nwg = ntiles > cu_count() ? cu_count() : ntiles;  // one per CU, at most one per tile
+  int nwg = ntiles > cu_count() ? cu_count() : ntiles;  // one per CU, at most one per tile
+  // (tuning build: fewer workgroups, so that a small launch gives each a long walk)
+  if (tuning().flow_wgs > 0 && tuning().flow_wgs < nwg) nwg = tuning().flow_wgs;
   // The pruning launch's box-sum planes, in the scratch the context lent the
   // search when it holds every job's (attach_scratch sized it with
   // flow_planes_need; a captured search that met a smaller one runs without):
@@ -2088,6 +2205,8 @@ static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const Sear
     table_bytes = table * FLOW_ENTRY_BYTES;
   }
   if (jb.planes) g_last_flow_table.store(table, std::memory_order_relaxed);
+  // The pre-bound (flow_fill) and its issue priority: on in every launch with planes.
+  const int pre = tuning().flow_pre != 0 ? 1 | (tuning().flow_pre_prio & 3) << 1 : 0;
   // 144: the pitch of the 4-block tiles 1080p +-32 gets (row addresses in
   // the ds_read2 offsets); any other pitch takes the runtime-pitch body
 #define ME_FLOW_CASE(PP)                                                                        \
@@ -2099,7 +2218,7 @@ static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const Sear
     if (e != hipSuccess) return e;                                                              \
     if (PP == 144 && g.prune && jb.planes)                                                      \
       hipLaunchKernelGGL((me_flow_chain_kernel<16, 13>), dim3((unsigned)nwg), dim3(1024), lds,  \
-                         stream, p, g, jb, table);                                              \
+                         stream, p, g, jb, table, pre);                                         \
     else                                                                                        \
       hipLaunchKernelGGL((me_flow_kernel<16, 13, PP>), dim3((unsigned)nwg), dim3(1024), lds,    \
                          stream, p, g, jb);                                                     \

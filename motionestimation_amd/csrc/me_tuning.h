@@ -47,6 +47,11 @@ struct Tuning {
   int flow_table = -1;    // ME_FLOW_TABLE=0|1: the slim launch's workgroups decode their items once into an LDS table
                           // (me_geom.h FlowEntry) off / on (-1 = automatic: on where the table fits)
   int flow_table_cap = 0; // ME_FLOW_TABLE_CAP=1..4096: a launch whose longest walk has more items runs without the table
+  int flow_pre = -1;      // ME_FLOW_PRE=0|1: the slim launch's publishing wave forms the bound's minlb of the slot's next
+                          // item behind the publish (the pre-bound, me_kernels.hip flow_fill) off / on (-1 = automatic: on)
+  int flow_pre_prio = 1;  // ME_FLOW_PRE_PRIO=0|1|3: the pre-bound's issue priority (1: above the tasks it runs beside, below
+                          // the post-bound and the staging at 3; measured best, profiles/prebound_prio_sweep.txt)
+  int flow_wgs = 0;       // ME_FLOW_WGS=1..1024: workgroups of a flow launch at most (0 = one per CU): long walks on small launches
   int prune_stats = 0;    // set by the tuning build: the flow kernel counts live / total lane-tasks and bypassed items
   int flow_one = -1;      // ME_FLOW_ONE=0|1: a batch's flow jobs in launches of one ring / in one launch (-1 = automatic: one)
   int mfma_s2k = -1;      // ME_MFMA_S2K=0|1: 16x16 SSD, S <= 64: S2 from the prepass plane / formed in

@@ -2,7 +2,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 CC    ?= gcc
 CXX   ?= g++
-all: bin/mes_hip bin/mes_seq bin/valu_microbench bin/flow_planes_dump bin/flow_job_dump bin/flow_slim_dump bin/flow_table_dump
+all: bin/mes_hip bin/mes_seq bin/valu_microbench bin/flow_planes_dump bin/flow_job_dump bin/flow_slim_dump bin/flow_table_dump bin/flow_prebound_dump
 
 # CPU harness of the launch tile -> job rule (me_geom.h alone)
 bin/flow_job_dump: tools/flow_job_dump.cc motionestimation_amd/csrc/me_geom.h
@@ -13,6 +13,11 @@ bin/flow_job_dump: tools/flow_job_dump.cc motionestimation_amd/csrc/me_geom.h
 bin/flow_table_dump: tools/flow_table_dump.cc motionestimation_amd/csrc/me_geom.h
 	mkdir -p bin
 	$(CXX) -O1 -std=c++17 -Wall -Imotionestimation_amd/csrc -o $@ tools/flow_table_dump.cc
+
+# CPU harness of the chain kernel's pre-bound: the cur blocks' addresses and the marker's place (me_geom.h alone)
+bin/flow_prebound_dump: tools/flow_prebound_dump.cc motionestimation_amd/csrc/me_geom.h
+	mkdir -p bin
+	$(CXX) -O1 -std=c++17 -Wall -Imotionestimation_amd/csrc -o $@ tools/flow_prebound_dump.cc
 
 # CPU harness of the box-sum planes' scratch sizing (the planner file alone)
 CSRC = motionestimation_amd/csrc

@@ -139,6 +139,18 @@ if nref:
               f"window wait {bsp[7] / nbd:.0f}, step 3 {bsp[4] / nbd:.0f}, step 4 {bsp[5] / nbd:.0f}")
         # the head of the line: a slot's publish to the start of its item's first executed wave-task
         print(f"publish -> first executed task: mean {bsp[8] / max(bsp[9], 1):.0f} cycles ({bsp[9]} items)")
+        # The chain kernel's pre-bound (words a build without it leaves 0): the
+        # refills' last task done -> publish, the pre-bounds behind a publish,
+        # and the post-bounds that found the slot's marker BUSY and waited.
+        if bsp[14]:
+            print(f"refill, last task done -> publish: mean {bsp[14] / nref:.0f} cycles ({nref} refills)")
+            print(f"pre-bounds {bsp[13]}: mean {bsp[12] / max(bsp[13], 1):.0f} cycles; post-bounds that waited on BUSY "
+                  f"{bsp[11]} of {nref} refills: mean {bsp[10] / max(bsp[11], 1):.0f} cycles a wait, "
+                  f"{bsp[10] / nref:.0f} a refill")
+        else:  # (the same interval from the timers every stamps build has)
+            dr = ws[:, 7] & ((1 << 40) - 1)
+            print(f"refill, decode + DMA wait + bound (last task done -> publish but for the records' write): "
+                  f"mean {(dr.sum() + ws[:, 0].sum() + ws[:, 1].sum()) / nref:.0f} cycles ({nref} refills)")
     # Per XCD: the tile -> item decode (flow_item: the job lookup and the item's
     # geometry) where a wave advances to its next item and where the refill
     # names the item it stages, beside what a refill and a task wait for.
