@@ -79,7 +79,7 @@ static Tuning read_tuning() {
   env_int("ME_PRUNE", 0, 2, &t.prune);
   env_int("ME_PRUNE_BYPASS", 0, 1, &t.prune_bypass);
   env_int("ME_PRUNE_PLANES", 0, 1, &t.prune_planes);
-  env_int("ME_PRUNE_SPLIT", 0, 1, &t.prune_split);
+  env_int("ME_PRUNE_SPLIT", 0, 2, &t.prune_split);
   env_int("ME_FLOW_TABLE", 0, 1, &t.flow_table);
   env_int("ME_FLOW_TABLE_CAP", 1, 4096, &t.flow_table_cap);
   env_int("ME_FLOW_PRE", 0, 1, &t.flow_pre);
@@ -830,7 +830,7 @@ extern "C" int me_debug_flow_pre_stats(me_ctx* c, uint32_t* out3) {
   return rc;
 }
 // ... and the executed wave-tasks of pruned launches by split class: run whole
-// (P = 1), with 2 and with 4 lanes per list entry (me_geom.h flow_split_parts).
+// (P = 1), with 2 and with 4 or more lanes per list entry (me_geom.h flow_split_parts).
 extern "C" int me_debug_prune_split_stats(me_ctx* c, uint32_t* out3) {
   if (!c || c->devs.empty() || !out3) return ME_EINVAL;
   Dev& d = c->devs[0];
@@ -840,6 +840,21 @@ extern "C" int me_debug_prune_split_stats(me_ctx* c, uint32_t* out3) {
   if (hipSetDevice(d.id) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
       hipMemcpy(out3, d.sched + me::SCHED_SPLIT, 12, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemset(d.sched + me::SCHED_SPLIT, 0, 12) != hipSuccess)
+    rc = ME_EDEVICE;
+  (void)hipSetDevice(prev);
+  return rc;
+}
+// ... and the executed wave-tasks of pruned launches' h = 16 items by the list
+// entries the task held: out64[n - 1] tasks with n = 1 .. 64 entries.
+extern "C" int me_debug_prune_split_hist(me_ctx* c, uint32_t* out64) {
+  if (!c || c->devs.empty() || !out64) return ME_EINVAL;
+  Dev& d = c->devs[0];
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  int rc = ME_OK;
+  if (hipSetDevice(d.id) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(out64, d.sched + me::SCHED_SPLIT_HIST, 256, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemset(d.sched + me::SCHED_SPLIT_HIST, 0, 256) != hipSuccess)
     rc = ME_EDEVICE;
   (void)hipSetDevice(prev);
   return rc;

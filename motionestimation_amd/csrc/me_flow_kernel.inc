@@ -90,6 +90,13 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
     }
     if (prune && tid >= 32 && tid < 36) ctl->stats[tid - 32] = 0;
     if (prune && tid >= 36 && tid < 39) ctl->split[tid - 36] = 0;
+    // (tuning build: executed wave-tasks of h = B items by list entries held, 64 counters behind the block
+    // and the table; their place is kept in the block, so the task loop holds no argument or pointer for them)
+    if (prune && g.prune_stats == 2) {
+      const uint32_t off = (uint32_t)(FLOW_CTL_BYTES + table * FLOW_ENTRY_BYTES);
+      reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(ctl) + off)[tid] = 0;
+      if (tid == 0) ctl->hist_off = off;
+    }
 #if ME_FLOW_CHAIN
     if (tid >= 39 && tid < 42) ctl->pre[tid - 39] = 0;
 #endif
@@ -108,7 +115,8 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
                                              ? PF_EARLY
                                              : 0) |
 #endif
-                                        (g.prune_split ? PF_SPLIT : 0));
+                                        (g.prune_split ? PF_SPLIT : 0) | (g.prune_split == 2 ? PF_SPLIT_124 : 0) |
+                                        (g.prune_stats == 2 ? PF_HIST : 0));
     }
   }
   for (int i = tid; i < NB * g.tb; i += (int)blockDim.x) keys[i] = ~0ull;
@@ -440,24 +448,37 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
           "s_setprio 1\n"
           "2:" ::"s"(nx), "s"(lim1), "s"(lim2) : "scc");
     };
-    // The task's class: 0 runs whole (below), 1 / 2 split by rows over 2 / 4
-    // lanes per list entry (flow_split_task; pruned h = B items only: an
-    // h = B/2 item's list is full).
-    int cls = 0;
+    // The rows a lane of the task takes: K runs it whole (below), 7, 4, 3, 2
+    // and 1 split it over 2, 4, 5, 7 and 13 lanes per list entry
+    // (flow_split_task; pruned h = B items only: an h = B/2 item's list is
+    // full).  cls: the counters' class, whole / 2 / 4 or more lanes per entry.
+    int rows = K;
 #ifdef ME_STAMPS
     const unsigned long long st_k0 = __builtin_amdgcn_s_memtime();
     if (lane == 0 && bid < (1 << 12)) atomicMin(&g_first[bid * 16 + slot], st_k0);
 #endif
     if constexpr (PC == 144) {
       const int n = nlive - 64 * t;
-      if ((pfl & PF_SPLIT) && it.h == B && n <= 32) cls = flow_split_parts(n) >> 1;
-      if ((pfl & PF_STATS) && lane == 0) atomicAdd(&ctl->split[cls], 1u);
-      if (cls == 2)
-        flow_split_task<B, K, PC, 4>(p, g, it, smem, buf, tile_off, keys + slot * g.tb, t, n, lc0c, pfl, lag_check);
-      else if (cls == 1)
-        flow_split_task<B, K, PC, 2>(p, g, it, smem, buf, tile_off, keys + slot * g.tb, t, n, lc0c, pfl, lag_check);
+      if ((pfl & PF_SPLIT) && it.h == B && n <= 32)
+        rows = (pfl & PF_SPLIT_124) ? flow_split_rows_124(n) : flow_split_rows(n);
+      if ((pfl & PF_STATS) && lane == 0) {
+        atomicAdd(&ctl->split[rows == K ? 0 : rows == 7 ? 1 : 2], 1u);
+        if ((pfl & PF_HIST) && it.h == B)
+          atomicAdd(reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(ctl) + ctl->hist_off) + min(n, 64) - 1, 1u);
+      }
+#define ME_SPLIT_TASK(R) \
+  flow_split_task<B, K, PC, R>(p, g, it, smem, buf, tile_off, keys + slot * g.tb, t, n, lc0c, pfl, lag_check)
+      if (rows == 1) ME_SPLIT_TASK(1);
+      else if (rows == 2) ME_SPLIT_TASK(2);
+      else if (rows == 3) ME_SPLIT_TASK(3);
+      else if (rows == 4) ME_SPLIT_TASK(4);
+      else if (rows == 7) ME_SPLIT_TASK(7);
+#undef ME_SPLIT_TASK
     }
-    if (cls == 0) {
+#ifdef ME_STAMPS
+    const int cls = rows == K ? 0 : rows == 7 ? 1 : 2;
+#endif
+    if (rows == K) {
     const bool live = 64 * t + lane < nlive;
     const uint16_t* llist = reinterpret_cast<const uint16_t*>(buf + g.tile_bytes + g.tb * B * B);
     const int i = pfl && live ? (int)llist[64 * t + lane] : 64 * t + lane;
@@ -643,6 +664,10 @@ __global__ __launch_bounds__(1024) void me_flow_kernel(SearchArgs p, QsadGeom g,
       __syncthreads();
       if (tid < 4) atomicAdd(p.sched + SCHED_PRUNE + tid, ctl->stats[tid]);
       if (tid >= 4 && tid < 7) atomicAdd(p.sched + SCHED_SPLIT + tid - 4, ctl->split[tid - 4]);
+      if ((ctl->pflags & PF_HIST) && tid >= 64 && tid < 128) {
+        const uint32_t v = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(ctl) + ctl->hist_off)[tid - 64];
+        if (v) atomicAdd(p.sched + SCHED_SPLIT_HIST + tid - 64, v);
+      }
 #if ME_FLOW_CHAIN
       if (tid >= 7 && tid < 10) atomicAdd(p.sched + SCHED_PRE + tid - 7, ctl->pre[tid - 7]);
 #endif

@@ -97,10 +97,11 @@ struct QsadGeom {
   // lane-task runs, the ring is flow_slots slots in lds bytes):
   int prune;         // 1: on; 2: verify (every lane-task runs, a wrongly dead one is reported)
   int prune_bypass;  // 1: after a run of items the bound could not thin, skip it and re-probe
-  int prune_stats;   // 1: live / total lane-tasks and bypassed items counted in sched[SCHED_PRUNE..]
+  int prune_stats;   // 1: live / total lane-tasks and bypassed items counted in sched[SCHED_PRUNE..]; 2 (set by the
+                     // launch): and the launch's LDS ends with FLOW_HIST_BYTES for the wave-task histogram
   int prune_slots;   // ring slots when pruning without box-sum planes (each slot carries FLOW_PRUNE_BYTES of bound scratch)
   int prune_lds;     // dynamic LDS bytes of that launch
-  int prune_split;   // 1: a pruned item's short wave-task is split by dy rows (flow_split_* below)
+  int prune_split;   // 1: a pruned item's short wave-task is split by dy rows (flow_split_* below); 2: by the earlier rule
   // The pruning launch WITH box-sum planes (FlowJobs::planes): its bound reads
   // the planes from global memory, a slot carries FLOW_SLIM_BYTES of scratch
   // (0 slots: the shape's plane loads could straddle a phase row, no such launch).
@@ -109,30 +110,72 @@ struct QsadGeom {
 };
 
 // ---- row split of a pruned item's partial wave-task (me_flow_kernel) ----
-// A wave-task holding n <= 32 list entries runs with P lanes per entry: lane l
-// takes entry l / P and part l % P, the dy rows [row0, row0 + rows) of the
-// entry's K = 13 row chunk.  The parts overlap by a row where that saves the
-// row masks of an exact partition: a candidate computed twice gives the same key.
+// A wave-task holding n <= 32 list entries runs with P lanes per entry, each
+// taking R of the dy rows of the entry's K = 13 row chunk.  The wave's 64 lanes
+// allow min(13, 64 / n) parts, so a lane needs ceil(13 / that) rows; the kernel
+// has an instance for R = 1, 2, 3, 4 and 7 (and the whole task, 13), so the 5
+// rows that n = 17 .. 21 could do with become 7:
+//   n       1..4  5..9  10..12  13..16  17..32  33..64
+//   R          1     2       3       4       7      13
+//   P         13     7       5       4       2       1
+// P = ceil(13 / R) depends on R alone (more parts would only repeat rows): lane
+// l takes entry l / P and part i = l % P, the rows [row0, row0 + R) with row0 =
+// min(i R, 13 - R).  The last part overlaps the one in front where R does not
+// divide 13: that saves the row masks of an exact partition, and a candidate
+// computed twice gives the same key.  Lanes from n P on repeat entry n - 1 and
+// merge nothing.  The fold column's candidate belongs to part 0.
 constexpr int FLOW_SPLIT_K = 13;
-constexpr int flow_split_parts(int n) { return n <= 16 ? 4 : n <= 32 ? 2 : 1; }
-constexpr int flow_split_rows(int P) { return P == 4 ? 4 : P == 2 ? 7 : FLOW_SPLIT_K; }
-constexpr int flow_split_row0(int P, int s) { return P == 4 ? 3 * s : P == 2 ? 6 * s : 0; }
-constexpr bool flow_split_covers(int P) {  // the parts' union is rows 0..12, none past them
+constexpr int flow_split_rows(int n) {  // (a compare chain: the kernel evaluates it per wave-task)
+  return n <= 4 ? 1 : n <= 9 ? 2 : n <= 12 ? 3 : n <= 16 ? 4 : n <= 32 ? 7 : FLOW_SPLIT_K;
+}
+constexpr int flow_split_parts_of(int R) { return (FLOW_SPLIT_K + R - 1) / R; }
+constexpr int flow_split_parts(int n) { return flow_split_parts_of(flow_split_rows(n)); }
+constexpr int flow_split_row0(int R, int i) { return i * R < FLOW_SPLIT_K - R ? i * R : FLOW_SPLIT_K - R; }
+// Lane `lane` of a task of n entries run with R rows per lane (R a constant of
+// the caller's instance: the division compiles to a multiply and a shift).
+struct FlowSplitLane {
+  int entry;  // list entry of the task, 0 .. n - 1
+  int row0;   // first of the lane's R rows of the chunk
+  bool live;  // the lane has an entry of its own: it merges its key
+  bool fold;  // ... and the fold column's candidate of the entry
+};
+constexpr FlowSplitLane flow_split_lane(int R, int lane, int n) {
+  const int P = flow_split_parts_of(R);
+  const int e = (int)((unsigned)lane / (unsigned)P), part = lane - e * P;
+  return FlowSplitLane{e < n ? e : n - 1, flow_split_row0(R, part), e < n, e < n && part == 0};
+}
+// The rule before the 13-way split (1, 2 or 4 lanes per entry): the tuning
+// build's ME_PRUNE_SPLIT=2 runs it from the same kernels.
+constexpr int flow_split_rows_124(int n) { return n <= 16 ? 4 : n <= 32 ? 7 : FLOW_SPLIT_K; }
+constexpr bool flow_split_instance(int R) { return R == 1 || R == 2 || R == 3 || R == 4 || R == 7 || R == FLOW_SPLIT_K; }
+constexpr bool flow_split_rule_holds() {  // the chain above is the rule stated in words
+  for (int n = 1; n <= 64; n++) {
+    const int room = 64 / n < FLOW_SPLIT_K ? 64 / n : FLOW_SPLIT_K;
+    int R = (FLOW_SPLIT_K + room - 1) / room;
+    while (!flow_split_instance(R)) R++;
+    if (flow_split_rows(n) != R) return false;
+  }
+  return true;
+}
+constexpr bool flow_split_covers(int R) {  // the parts' union is rows 0..12, none past them
   unsigned m = 0;
-  for (int s = 0; s < P; s++)
-    for (int j = 0; j < flow_split_rows(P); j++) {
-      if (flow_split_row0(P, s) + j >= FLOW_SPLIT_K) return false;
-      m |= 1u << (flow_split_row0(P, s) + j);
+  for (int s = 0; s < flow_split_parts_of(R); s++)
+    for (int j = 0; j < R; j++) {
+      if (flow_split_row0(R, s) + j >= FLOW_SPLIT_K) return false;
+      m |= 1u << (flow_split_row0(R, s) + j);
     }
   return m == (1u << FLOW_SPLIT_K) - 1;
 }
-constexpr bool flow_split_fits(int P) {  // every n mapped to P has its P * n lanes in the wave
+constexpr bool flow_split_fits() {  // every n has its P * n lanes in the wave, under either rule
   for (int n = 1; n <= 64; n++)
-    if (flow_split_parts(n) == P && n * P > 64) return false;
+    if (n * flow_split_parts(n) > 64 || n * flow_split_parts_of(flow_split_rows_124(n)) > 64) return false;
   return true;
 }
-static_assert(flow_split_covers(1) && flow_split_covers(2) && flow_split_covers(4), "parts cover rows 0..12");
-static_assert(flow_split_fits(1) && flow_split_fits(2) && flow_split_fits(4), "64 / P >= the largest n of P");
+static_assert(flow_split_rule_holds(), "R = ceil(13 / min(13, 64 / n)), rounded up to an instance");
+static_assert(flow_split_covers(1) && flow_split_covers(2) && flow_split_covers(3) && flow_split_covers(4) &&
+                  flow_split_covers(7) && flow_split_covers(13),
+              "parts cover rows 0..12");
+static_assert(flow_split_fits(), "64 / P >= the largest n of P");
 
 // Bound scratch of one ring slot of the pruning flow kernel: four x-phase
 // planes of 77 rows x 32 box-sum bytes (the live list overlays them once the
@@ -148,6 +191,7 @@ constexpr int FLOW_PRUNE_MINLB = 4 * FLOW_PRUNE_PLANE;
 constexpr int FLOW_PRUNE_QCUR = FLOW_PRUNE_MINLB + 320 * 4;
 constexpr int FLOW_PRUNE_BYTES = FLOW_PRUNE_QCUR + 64;
 constexpr int FLOW_CTL_BYTES = 256;  // the pruning launch's control block (FlowCtl)
+constexpr int FLOW_HIST_BYTES = 256; // tuning build: 64 counters behind the control block and the item table
 // The slim bound scratch of a launch with box-sum planes: the bound's step 2
 // loads its plane rows from the job's planes in global memory into registers
 // (flow_plane_byte below), so the slot keeps only what outlives the bound or

@@ -18,16 +18,21 @@ namespace me {
 // [SCHED_ARRIVE] its arrivals (the last workgroup out re-zeroes [0, 17)),
 // [SCHED_ERR]: a kernel whose bounded wait expired sets it (the host reads and
 // clears it: device_status, me_device_check).
-constexpr int SCHED_WORDS = 32;
+constexpr int SCHED_WORDS = 96;
 constexpr int SCHED_ARRIVE = 16;
 constexpr int SCHED_ERR = 31;
 // Tuning build only (QsadGeom::prune_stats): the pruning flow kernel's counts
 // since the words were last zeroed: live lane-tasks, all lane-tasks, items
 // whose bound was bypassed, items.
 constexpr int SCHED_PRUNE = 24;
-// ... and its executed wave-tasks run whole, with 2 and with 4 lanes per list
-// entry (the row split, me_geom.h flow_split_parts): three words.
+// ... and its executed wave-tasks run whole, with 2 and with 4 or more lanes per
+// list entry (the row split, me_geom.h flow_split_parts): three words.
 constexpr int SCHED_SPLIT = 28;
+// ... and those of its h = B items by the list entries n = 1 .. 64 the task
+// held (word n - 1; a bypassed item's tasks hold 64): what the row split's rule
+// is chosen from.
+constexpr int SCHED_SPLIT_HIST = 32;
+static_assert(SCHED_SPLIT_HIST + 64 <= SCHED_WORDS, "the histogram lies inside sched");
 // ... and the chain kernel's pre-bound (flow_fill): items pre-bound, items whose
 // post-bound met the marker BUSY, items that fell back (bounded items of a slot's
 // second or later turn that found no pre-bound and ran the whole bound): three words.

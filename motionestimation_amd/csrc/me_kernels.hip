@@ -968,21 +968,25 @@ struct FlowCtl {
   // pruning launches only (the plain launch's LDS ends above)
   uint32_t live[16];   // live lane-tasks of the slot's item (its list's length)
   uint32_t stats[4];   // tuning build: live, all lane-tasks, bypassed items, items (flushed at the end)
-  uint32_t split[3];   // tuning build: executed wave-tasks run with 1, 2, 4 lanes per list entry
+  uint32_t split[3];   // tuning build: executed wave-tasks run whole, with 2 and with 4 or more lanes per list entry
+  uint32_t hist_off;   // tuning build (PF_HIST): bytes from this block to the launch's 64 counters of executed wave-tasks of
+                       // h = B items by list entries held (sched[SCHED_SPLIT_HIST ..])
   uint32_t pre[3];     // tuning build, chain kernel: items pre-bound, post-bounds that met BUSY, items that fell back (a bounded
                        // item of a slot's second or later turn whose marker named no pre-bound: it ran the whole bound)
 };
 // PF_PLANES: the launch has box-sum planes (FlowJobs::planes): flow_bound skips
 // its step 1 and loads the plane rows of step 2 from them (the slim scratch).
 // PF_SPLIT: a pruned item's wave-task of <= 32 list entries is split by rows
-// (flow_split_task below).
+// (flow_split_task below); PF_SPLIT_124: by the earlier rule of 1, 2 or 4 lanes
+// per entry (the tuning build's A/B).
 // PF_TABLE: the workgroup's items are decoded in the LDS item table behind this
 // block (me_geom.h FlowEntry).  PF_EARLY: a slot's fill issues the window DMA
 // last and starts the bound under it (flow_fill below).  PF_PRE: the wave that
 // publishes an item forms the bound's minlb of the slot's next item behind the
 // publish (the pre-bound, flow_fill below); PF_PRE_PRIO: its issue priority.
 enum { PF_ON = 1, PF_VERIFY = 2, PF_BYPASS = 4, PF_STATS = 8, PF_PLANES = 16, PF_SPLIT = 32, PF_TABLE = 64,
-       PF_EARLY = 128, PF_PRE = 256, PF_PRE_PRIO_SHIFT = 9, PF_PRE_PRIO = 3 << PF_PRE_PRIO_SHIFT };
+       PF_EARLY = 128, PF_PRE = 256, PF_PRE_PRIO_SHIFT = 9, PF_PRE_PRIO = 3 << PF_PRE_PRIO_SHIFT,
+       PF_SPLIT_124 = 2048, PF_HIST = 4096 };  // (PF_HIST: QsadGeom::prune_stats == 2)
 static_assert(sizeof(FlowCtl) <= FLOW_CTL_BYTES, "control block of the pruning launch");
 
 // Tile of the flow kernel's launch -> its item (all dy chunks: one pass).  A
@@ -1727,28 +1731,30 @@ __device__ __forceinline__ void flow_bound(const SearchArgs& p, const QsadGeom& 
 // Task t of a pruned h = B item whose list has n <= 32 entries left for it
 // (almost every executed task of correlated content: 9 live lane-tasks of 320
 // per item on the bench input) would issue all 64 lanes' 13 dy rows for n live
-// ones.  Split by rows instead (me_geom.h flow_split_*): P = 4 or 2 lanes per
-// entry, lane l = entry l / P, part l % P, rows [j0, j0 + KP) of the entry's
-// chunk: 16 (KP + 15)-row window walks of 4 KP qsads instead of 52.  The parts'
-// keys meet in the block's keys word like those of different lane-tasks; rows
-// two parts share give the same key twice.  The fold column's candidate runs
+// ones.  Split by rows instead (me_geom.h flow_split_*): an instance per rows a
+// lane takes, R = 1, 2, 3, 4 or 7, with P = ceil(13 / R) lanes per entry; lane l
+// = entry l / P, part l % P, rows [j0, j0 + R) of the entry's chunk: an (R + 15)-row
+// window walk of 64 R qsads instead of 28 rows and 832.  The parts' keys meet in
+// the block's keys word like those of different lane-tasks; rows two parts
+// share give the same key twice.  The fold column's candidate runs
 // in part 0 (j0 = 0: its row index is the chunk's).  A lane past the entries
 // repeats the last one (so it raises no edge mask of its own) and merges nothing.
 // The whole body, list read to key merge, lives here: nothing of it is live
 // across the unsplit task's K = 13 row loop.
-template <int B, int K, int PC, int P, typename Hook>
+template <int B, int K, int PC, int KP, typename Hook>
 __device__ __forceinline__ void flow_split_task(const SearchArgs& p, const QsadGeom& g, const Item& it,
                                                 const uint8_t* smem, const uint8_t* buf, uint32_t tile_off,
                                                 uint64_t* keys, int t, int n, int lc0c, int pfl,
                                                 Hook lag_check) {
-  constexpr int CW = B / 4, KP = flow_split_rows(P);
-  static_assert(K == FLOW_SPLIT_K && CW == 4, "the split's row rules");
+  constexpr int CW = B / 4;
+  static_assert(K == FLOW_SPLIT_K && CW == 4 && KP < K && flow_split_instance(KP), "the split's row rules");
   const int S = p.range, G = g.groups;
   const int lane = fresh_tid() & 63;
-  const int e = lane / P, j0 = flow_split_row0(P, lane & (P - 1));
-  const bool live = e < n;
+  const FlowSplitLane sl = flow_split_lane(KP, lane, n);
+  const int j0 = sl.row0;  // (0 in part 0 alone: the fold candidate's lane)
+  const bool live = sl.live;
   const uint8_t* pv = buf + g.tile_bytes + g.tb * B * B;
-  const int i = (int)reinterpret_cast<const uint16_t*>(pv)[64 * t + (live ? e : n - 1)];
+  const int i = (int)reinterpret_cast<const uint16_t*>(pv)[64 * t + sl.entry];
   const int bg = (int)__umulhi((uint32_t)i, g.magic_groups);  // i / G
   const int gi = i - bg * G;
   const uint32_t magic_nb = 0xFFFFFFFFu / (uint32_t)it.nb + 1u;
@@ -2161,8 +2167,9 @@ int last_flow_table() { return g_last_flow_table.load(std::memory_order_relaxed)
 
 // One flow-kernel launch over jobs [0, n) (full-height rows and h = B/2
 // bottom rows only; n <= MAX_JOBS).
-static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const SearchJob* jobs, int n,
+static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& plan, const SearchJob* jobs, int n,
                               hipStream_t stream) {
+  QsadGeom g = plan;
   FlowJobs jb = job_table(p, g.wg_per_row, jobs, n);
   const int ntiles = jb.tile_pre[jb.n];
   if (ntiles <= 0) return hipSuccess;
@@ -2205,13 +2212,22 @@ static hipError_t launch_flow(const SearchArgs& p, const QsadGeom& g, const Sear
     table_bytes = table * FLOW_ENTRY_BYTES;
   }
   if (jb.planes) g_last_flow_table.store(table, std::memory_order_relaxed);
+  // Tuning build: the counting launch keeps its histogram of executed wave-tasks
+  // (SCHED_SPLIT_HIST) in 64 words of LDS behind all that, where they fit, and
+  // says so in prune_stats.
+  int hist_bytes = 0;
+  if (g.pitch == 144 && g.prune && g.prune_stats &&
+      (jb.planes ? g.slim_lds + table_bytes : g.prune_lds) + FLOW_HIST_BYTES <= FLOW_LDS_BUDGET) {
+    hist_bytes = FLOW_HIST_BYTES;
+    g.prune_stats = 2;
+  }
   // The pre-bound (flow_fill) and its issue priority: on in every launch with planes.
   const int pre = tuning().flow_pre != 0 ? 1 | (tuning().flow_pre_prio & 3) << 1 : 0;
   // 144: the pitch of the 4-block tiles 1080p +-32 gets (row addresses in
   // the ds_read2 offsets); any other pitch takes the runtime-pitch body
 #define ME_FLOW_CASE(PP)                                                                        \
   if (PP == 0 || g.pitch == PP) {                                                               \
-    const int lds = !(PP == 144 && g.prune) ? g.lds : jb.planes ? g.slim_lds + table_bytes : g.prune_lds; \
+    const int lds = !(PP == 144 && g.prune) ? g.lds : (jb.planes ? g.slim_lds + table_bytes : g.prune_lds) + hist_bytes; \
     const void* fn = PP == 144 && g.prune && jb.planes ? (const void*)me_flow_chain_kernel<16, 13> \
                                                        : (const void*)me_flow_kernel<16, 13, PP>; \
     const hipError_t e = lds_attr(fn, lds);                                                     \

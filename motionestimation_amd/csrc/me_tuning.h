@@ -42,8 +42,9 @@ struct Tuning {
   int prune_bypass = -1;  // ME_PRUNE_BYPASS=0|1: skip the bound after a run of items it could not thin (-1 = automatic: on)
   int prune_planes = -1;  // ME_PRUNE_PLANES=0|1: the bound's box sums computed in the flow kernel / read from the per-frame
                           // planes of the box-sum prepass (-1 = automatic: flow_planes_on, me_valu_plan.cpp)
-  int prune_split = -1;   // ME_PRUNE_SPLIT=0|1: a pruned item's wave-task of <= 32 list entries runs whole / split by dy rows
-                          // over 2 or 4 lanes per entry (me_geom.h flow_split_*) (-1 = automatic: on)
+  int prune_split = -1;   // ME_PRUNE_SPLIT=0|1|2: a pruned item's wave-task of <= 32 list entries runs whole / split by dy rows
+                          // over 2 to 13 lanes per entry (me_geom.h flow_split_*) / split over 2 or 4 only, the earlier rule
+                          // (-1 = automatic: 1)
   int flow_table = -1;    // ME_FLOW_TABLE=0|1: the slim launch's workgroups decode their items once into an LDS table
                           // (me_geom.h FlowEntry) off / on (-1 = automatic: on where the table fits)
   int flow_table_cap = 0; // ME_FLOW_TABLE_CAP=1..4096: a launch whose longest walk has more items runs without the table

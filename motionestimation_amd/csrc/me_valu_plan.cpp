@@ -387,7 +387,7 @@ bool plan_flow(const PlanShape& s, int cus, const Tuning& tu, QsadGeom* g) {
       q.prune = tu.prune == 2 ? 2 : 1;
       q.prune_bypass = tu.prune_bypass != 0;
       q.prune_stats = tu.prune_stats;
-      q.prune_split = tu.prune_split != 0;
+      q.prune_split = tu.prune_split == 2 ? 2 : tu.prune_split != 0;
       q.prune_slots = ns;
       q.prune_lds = ns * pslot + ns * q.tb * 8 + FLOW_CTL_BYTES;
       // With box-sum planes the bound reads them from global memory and a slot

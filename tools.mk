@@ -2,7 +2,12 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 CC    ?= gcc
 CXX   ?= g++
-all: bin/mes_hip bin/mes_seq bin/valu_microbench bin/flow_planes_dump bin/flow_job_dump bin/flow_slim_dump bin/flow_table_dump bin/flow_prebound_dump
+all: bin/mes_hip bin/mes_seq bin/valu_microbench bin/flow_planes_dump bin/flow_job_dump bin/flow_slim_dump bin/flow_table_dump bin/flow_prebound_dump bin/flow_split_dump
+
+# CPU harness of the row split's rule: lanes -> (list entry, dy rows) (me_geom.h alone)
+bin/flow_split_dump: tools/flow_split_dump.cc motionestimation_amd/csrc/me_geom.h
+	mkdir -p bin
+	$(CXX) -O1 -std=c++17 -Wall -Imotionestimation_amd/csrc -o $@ tools/flow_split_dump.cc
 
 # CPU harness of the launch tile -> job rule (me_geom.h alone)
 bin/flow_job_dump: tools/flow_job_dump.cc motionestimation_amd/csrc/me_geom.h

@@ -121,8 +121,9 @@ if nref:
     print(f"refills {nref}: DMA wait mean {ws[:, 0].sum() / nref:.0f} cycles, stage-to-publish after it "
           f"(bound phase) mean {ws[:, 1].sum() / nref:.0f} cycles; spin per task mean {spin.sum() / max(ntask.sum(), 1):.0f}")
     # Executed wave-tasks (list read to key merge) by row-split class: run
-    # whole, with 2 and with 4 lanes per list entry; word = count << 40 | cycles.
-    for col, name in ((3, "whole"), (4, "2 lanes/entry"), (5, "4 lanes/entry")):
+    # whole, with 2 (7 rows a lane) and with 4 to 13 lanes per list entry (4 to 1
+    # rows; ME_PRUNE_SPLIT=2: 4 lanes, 4 rows); word = count << 40 | cycles.
+    for col, name in ((3, "whole"), (4, "2 lanes/entry"), (5, "4 or more lanes/entry")):
         cnt, cyc = (ws[:, col] >> 40).sum(), (ws[:, col] & ((1 << 40) - 1)).sum()
         print(f"executed wave-tasks {name}: {cnt}" + (f", mean {cyc / cnt:.0f} cycles" if cnt else ""))
     # The bound of a refill, split (g_bstamps, cycles per bounded item): cur q

@@ -14,7 +14,10 @@ median and min-max of the per-call time over the rounds, and whether every
 library's fields are equal array for array.  A tuning build
 (libme_hip_tune.so; ME_PRUNE, ME_PRUNE_BYPASS, ME_PRUNE_SPLIT, ME_FLOW_SLOTS,
 ME_FAIR_T pass through from the environment) also reports its live lane-task
-fraction, bypassed items and executed wave-tasks by row-split class per call.
+fraction, bypassed items and executed wave-tasks by row-split class per call,
+and (a build with me_debug_prune_split_hist) those of h = 16 items by the list
+entries they held, n = 1 .. 64 (tasks_by_n), and by the rows a lane takes under
+the rule ME_PRUNE_SPLIT selects (tasks_by_rows).
 usage: python3 tools/sad_prune_ab.py --libs libme_hip_parent.so,libme_hip.so [--rounds 5]
        [--inputs synth,foreman,noise] [--ms 300]"""
 import argparse
@@ -51,6 +54,24 @@ def frames_of(name):
     raise SystemExit(f"unknown input {name}")
 
 
+def split_rows(n, rule="1"):
+    """Rows of the chunk's 13 a lane takes in a task of n list entries (csrc/me_geom.h
+    flow_split_rows; rule "2": flow_split_rows_124, "0": no split)."""
+    if rule == "0" or n > 32:
+        return 13
+    if rule == "2":
+        return 4 if n <= 16 else 7
+    return 1 if n <= 4 else 2 if n <= 9 else 3 if n <= 12 else 4 if n <= 16 else 7
+
+
+def tasks_by_rows(by_n, rule="1"):
+    out = {}
+    for i, c in enumerate(by_n):
+        r = str(split_rows(i + 1, rule))
+        out[r] = out.get(r, 0) + c
+    return out
+
+
 def child(a):
     import numpy as np
     import torch
@@ -81,14 +102,23 @@ def child(a):
         if split:
             L.me_debug_prune_split_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
             L.me_debug_prune_split_stats(eng._h, out3)
+        hist = hasattr(L, "me_debug_prune_split_hist")
+        out64 = (ctypes.c_uint32 * 64)()
+        if hist:
+            L.me_debug_prune_split_hist.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+            L.me_debug_prune_split_hist(eng._h, out64)
         run()
         torch.cuda.synchronize()
         L.me_debug_prune_stats(eng._h, out)
         stats = {"live": out[0], "total": out[1], "bypassed_items": out[2], "items": out[3],
                  "live_frac": out[0] / out[1] if out[1] else None}
-        if split:  # executed wave-tasks run whole / with 2 / with 4 lanes per list entry
+        if split:  # executed wave-tasks run whole / with 2 / with 4 or more lanes per list entry
             L.me_debug_prune_split_stats(eng._h, out3)
             stats["tasks_p1_p2_p4"] = list(out3)
+        if hist:  # ... of h = 16 items by list entries held, n = 1 .. 64, and by the rows a lane takes
+            L.me_debug_prune_split_hist(eng._h, out64)
+            stats["tasks_by_n"] = list(out64)
+            stats["tasks_by_rows"] = tasks_by_rows(list(out64), os.environ.get("ME_PRUNE_SPLIT", "1"))
     reps = 0
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
