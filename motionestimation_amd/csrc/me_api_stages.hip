@@ -568,7 +568,7 @@ me_status me_full_search_rd_qpel(me_ctx* c, const uint8_t* ref, const uint8_t* c
   return download_all(c, d, L, out, true);
 }
 
-// ---- rate-constrained partition search (me_partition_rd.hip) ----
+// ---- rate-constrained partition search (me_partition.hip) ----
 
 me_status me_partition_rd_search_device(me_ctx* c, const uint8_t* d_ref, size_t ref_frame_stride,
                                         const uint8_t* d_cur, size_t cur_frame_stride, int width,

@@ -138,7 +138,7 @@ struct FrameBatch {
   int width, height, stride, blk, n_frames;
 };
 
-// Partition search (me_partition.hip; geometry in me_partition.h).
+// Partition search (me_partition.hip; geometry in me_tile_geom.h).
 // out: device pointers (host struct).
 hipError_t launch_partition_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,
                                    const me_part_fields& out, hipStream_t stream);
@@ -157,13 +157,14 @@ hipError_t launch_qpel_refine(const FrameBatch& b, int cost, const int16_t* mv_i
 hipError_t launch_qpel_refine_rd(const FrameBatch& b, int cost, uint32_t lambda, const int16_t* pred,
                                  const int16_t* mv_in, int16_t* mv_out, uint32_t* cost_out,
                                  uint32_t* dist_out, hipStream_t stream);
-// Rate-constrained integer search (me_rd.hip; geometry in me_rd.h).  Records
+// Rate-constrained integer search (me_rd.hip; geometry in me_tile_geom.h and
+// me_rd.h).  Records
 // and predictors (null: all zero) at + f * nblk (x 2 for vectors); dist and
 // bits may be null.
 hipError_t launch_rd_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,
                             const int16_t* pred, int16_t* mv, uint32_t* cost, uint32_t* dist,
                             uint8_t* bits, hipStream_t stream);
-// Rate-constrained partition search (me_partition_rd.hip): launch_partition_search
+// Rate-constrained partition search (me_partition.hip): launch_partition_search
 // on J_p = SAD_p + lambda * bits(4 d - pred), pred [n_frames][nby][nbx][2]
 // quarter-pel or null (all zero).
 hipError_t launch_partition_rd_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,

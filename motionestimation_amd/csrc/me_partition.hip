@@ -1,6 +1,7 @@
-// me_partition.hip -- variable-block-size partition search with mode decision
-// (include/me.h "partition search"; DESIGN.md "Partition search").  No
-// reference counterpart: the reference searches one block size per run.
+// me_partition.hip -- variable-block-size partition search with mode decision,
+// plain and rate-constrained (include/me.h "partition search", "rate-constrained
+// partition search"; DESIGN.md under the same names).  No reference
+// counterpart: the reference searches one block size per run.
 //
 // For every candidate displacement of a B x B macroblock the SADs of its four
 // h x h quadrants (h = B / 2) are formed once; the halves and the whole are
@@ -11,31 +12,51 @@
 // first displacement in raster order.  The mode decision runs in the same
 // launch, by the thread that writes a macroblock's records.
 //
-// Kernels:
-//   me_part_fast_kernel<K>  B = 16, full-size macroblocks, S <= 64, rows a
-//                           multiple of 4 bytes.  The me_fast_kernel scheme:
-//                           a workgroup takes PART_TB macroblocks of one row,
-//                           their union window is staged once in LDS by LDS
-//                           DMA, a lane holds its macroblock in 64 VGPRs and
-//                           owns 4 dx x K dy candidates, walking the K + 15
-//                           window rows with v_qsad_pk_u16_u8.  Per dy row four
-//                           packed-u16 quadrant accumulators (segments 0-1 /
-//                           2-3 of a row are left / right, rows 0-7 / 8-15 top
-//                           / bottom): 8 VGPRs, the same 64 qsads as a plain
-//                           16 x 16 search.  (The row walk, part_lane, lives in
-//                           me_partition_lane.h: me_partition_rd.hip shares it.)
-//   me_part_generic_kernel  B in {8, 16, 32}, any S <= 128, clipped
-//                           macroblocks, any pitch: one workgroup per
-//                           macroblock, one candidate per lane per step,
-//                           v_sad_u8 into u32 quadrant sums.
-//   me_part_leaf_kernel     the leaf field from the four fields and the modes.
+// The rate-constrained search has J_p(d) = SAD_p(d) + lambda R(d) in the nine
+// minima, R(d) = bits(4 dx - px) + bits(4 dy - py) against the macroblock's
+// quarter-pel predictor (rd_bits of me_rd.h): one rate per displacement, shared
+// by the nine partitions.  The writing thread recomputes R from each winning
+// displacement (dist = J - lambda R) and decides the mode on sum J_p + lambda
+// mbits(m), mbits = (1, 3, 3, 5) against the plain search's (1, 2, 2, 4).
+//
+// Kernels (the building blocks are me_tile_search.h's):
+//   me_part_fast_kernel<K>     B = 16, full-size macroblocks, S <= 64, rows a
+//                              multiple of 4 bytes.  A workgroup takes TILE_TB
+//                              macroblocks of one row, their union window is
+//                              staged once in LDS by LDS DMA, a lane holds its
+//                              macroblock in 64 VGPRs and owns 4 dx x K dy
+//                              candidates, walking the K + 15 window rows with
+//                              v_qsad_pk_u16_u8 into four packed-u16 quadrant
+//                              accumulators per dy row (tile_lane<K, 4>): 8
+//                              VGPRs, the same 64 qsads as a plain 16 x 16
+//                              search.  Candidates outside the frame are masked.
+//   me_part_rd_fast_kernel<K>  the same, lambda <= ME_RD_FAST_MAX_LAMBDA, with
+//                              me_rd_fast_kernel's rate tables in LDS: lambda
+//                              bits(4 dx - px) per window column and lambda
+//                              bits(4 dy - py) per row of every macroblock, ~0
+//                              where the column or row is no candidate.  Per dy
+//                              row and dx one saturating r = rx + ry, then per
+//                              partition one saturating J = sad + r and the
+//                              lane key J << 6 | 4 j + i: an invalid
+//                              candidate's J is ~0, its key at least
+//                              0xFFFFFFC0, above every valid one (J < 2^26 -
+//                              1); no compare, mask or branch per candidate.
+//   me_tile_generic_kernel<4, false, PartOut, part_store> and
+//   me_tile_generic_kernel<4, true, PartRdOut, part_rd_store>
+//                              B in {8, 16, 32}, any S <= 128, clipped
+//                              macroblocks, any pitch (and lambda): one
+//                              workgroup per macroblock, one candidate per lane
+//                              per step, v_sad_u8 into u32 quadrant sums, R per
+//                              candidate.
+//   me_part_leaf_kernel        the leaf field from the four fields and the modes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "me.h"
 #include "me_kernels.h"
 #include "me_partition.h"
-#include "me_partition_lane.h"
+#include "me_rd.h"
+#include "me_tile_search.h"
 
 namespace me {
 namespace {
@@ -46,139 +67,97 @@ struct PartOut {
   uint32_t lambda;
 };
 
-// A cell's record from its key (make_key / store_mv of me_kernels.h).
-__device__ __forceinline__ void store_rec(int16_t* mv, uint32_t* cost, size_t at, uint64_t key) {
-  store_mv(mv + 2 * at, 0, key);
-  if (cost) cost[at] = (uint32_t)(key >> 32);
-}
+struct PartRdOut {
+  me_part_rd_fields f;
+  const int16_t* pred;  // null: all zero
+  int nbx, nby, nhx, nhy;
+  uint32_t lambda;
+};
 
-// Records and mode of macroblock (bx, by) of frame f from its nine keys.  A
-// partition exists iff its cell is inside its grid; the quadrant sums of the
-// missing ones are 0, so the mode costs need no special case.
-__device__ __forceinline__ void part_store(const PartOut& o, int f, int bx, int by,
-                                           const uint64_t* k) {
+// The nine cells of macroblock (bx, by) of frame f in their grids (2Nx2N, 2NxN,
+// Nx2N, NxN: grid_of).  A partition exists iff its cell is inside its grid.
+struct PartCells {
+  size_t at[P_N];
+  bool there[P_N];
+};
+__device__ __forceinline__ constexpr int grid_of(int p) {
+  return p == P_FULL ? 0 : p <= P_BOT ? 1 : p <= P_RIGHT ? 2 : 3;
+}
+template <typename Out>
+__device__ __forceinline__ PartCells part_cells(const Out& o, int f, int bx, int by) {
   const size_t f0 = (size_t)f * o.nbx * o.nby, f1 = (size_t)f * o.nbx * o.nhy;
   const size_t f2 = (size_t)f * o.nhx * o.nby, f3 = (size_t)f * o.nhx * o.nhy;
   const bool right = 2 * bx + 1 < o.nhx, bottom = 2 * by + 1 < o.nhy;
-  const size_t mb = f0 + (size_t)by * o.nbx + bx;
-  store_rec(o.f.mv_2nx2n, o.f.cost_2nx2n, mb, k[P_FULL]);
-  store_rec(o.f.mv_2nxn, o.f.cost_2nxn, f1 + (size_t)(2 * by) * o.nbx + bx, k[P_TOP]);
-  if (bottom)
-    store_rec(o.f.mv_2nxn, o.f.cost_2nxn, f1 + (size_t)(2 * by + 1) * o.nbx + bx, k[P_BOT]);
-  store_rec(o.f.mv_nx2n, o.f.cost_nx2n, f2 + (size_t)by * o.nhx + 2 * bx, k[P_LEFT]);
-  if (right) store_rec(o.f.mv_nx2n, o.f.cost_nx2n, f2 + (size_t)by * o.nhx + 2 * bx + 1, k[P_RIGHT]);
   const size_t q = f3 + (size_t)(2 * by) * o.nhx + 2 * bx;
-  store_rec(o.f.mv_nxn, o.f.cost_nxn, q, k[P_TL]);
-  if (right) store_rec(o.f.mv_nxn, o.f.cost_nxn, q + 1, k[P_TR]);
-  if (bottom) store_rec(o.f.mv_nxn, o.f.cost_nxn, q + o.nhx, k[P_BL]);
-  if (right && bottom) store_rec(o.f.mv_nxn, o.f.cost_nxn, q + o.nhx + 1, k[P_BR]);
+  return {{f0 + (size_t)by * o.nbx + bx, f1 + (size_t)(2 * by) * o.nbx + bx,
+           f1 + (size_t)(2 * by + 1) * o.nbx + bx, f2 + (size_t)by * o.nhx + 2 * bx,
+           f2 + (size_t)by * o.nhx + 2 * bx + 1, q, q + 1, q + o.nhx, q + o.nhx + 1},
+          {true, true, bottom, true, right, true, right, bottom, right && bottom}};
+}
 
-  auto c = [&](int p, bool there) { return there ? (uint32_t)(k[p] >> 32) : 0u; };
-  const uint32_t j0 = c(P_FULL, true) + o.lambda;
-  const uint32_t j1 = c(P_TOP, true) + c(P_BOT, bottom) + 2 * o.lambda;
-  const uint32_t j2 = c(P_LEFT, true) + c(P_RIGHT, right) + 2 * o.lambda;
-  const uint32_t j3 = c(P_TL, true) + c(P_TR, right) + c(P_BL, bottom) + c(P_BR, right && bottom) +
-                      4 * o.lambda;
-  uint32_t best = j0;
+// Macroblock mb's mode from its partitions' costs j (0 for the missing ones, so
+// the sums need no special case) and the modes' penalties lambda x (1, half,
+// half, quarter).
+__device__ __forceinline__ void part_mode(const me_part_fields& F, size_t mb, const uint32_t (&j)[P_N],
+                                          uint32_t lambda, uint32_t half, uint32_t quarter) {
+  const uint32_t j1 = j[P_TOP] + j[P_BOT] + half * lambda;
+  const uint32_t j2 = j[P_LEFT] + j[P_RIGHT] + half * lambda;
+  const uint32_t j3 = j[P_TL] + j[P_TR] + j[P_BL] + j[P_BR] + quarter * lambda;
+  uint32_t best = j[P_FULL] + lambda;
   int mode = ME_PART_2Nx2N;
   if (j1 < best) best = j1, mode = ME_PART_2NxN;
   if (j2 < best) best = j2, mode = ME_PART_Nx2N;
   if (j3 < best) best = j3, mode = ME_PART_NxN;
-  o.f.mode[mb] = (uint8_t)mode;
-  if (o.f.mode_cost) o.f.mode_cost[mb] = best;
+  F.mode[mb] = (uint8_t)mode;
+  if (F.mode_cost) F.mode_cost[mb] = best;
 }
 
-// ------------------------------------------------------------------ generic
-constexpr int GEN_THREADS = 256;
-
-// One workgroup per macroblock (blockIdx.x) and frame (blockIdx.y).  The
-// current block sits in LDS as rows of B bytes, zero beyond the clipped size;
-// the reference is read from memory, bytes beyond the clipped block never.
-// nbx_skip x nby_skip: the full-size macroblocks the fast kernel took (0 x 0:
-// none); the grid then counts the rim only, the right columns of every
-// macroblock row first, then the bottom rows' other macroblocks.
-__global__ __launch_bounds__(GEN_THREADS) void me_part_generic_kernel(
-    const uint8_t* __restrict__ ref, size_t ref_frame_stride, const uint8_t* __restrict__ cur,
-    size_t cur_frame_stride, int width, int height, int stride, int B, int S, int nbx_skip,
-    int nby_skip, PartOut o) {
-  __shared__ uint32_t cblk[32 * 8];
-  __shared__ uint64_t red[GEN_THREADS / 64][P_N];
-  const int tid = threadIdx.x, f = blockIdx.y;
-  int bx = (int)blockIdx.x % o.nbx, by = (int)blockIdx.x / o.nbx;
-  if (nbx_skip > 0) {
-    const int right = o.nbx - nbx_skip, i = (int)blockIdx.x - right * o.nby;
-    if (i < 0) {
-      bx = nbx_skip + (int)blockIdx.x % right, by = (int)blockIdx.x / right;
-    } else {
-      bx = i % nbx_skip, by = nby_skip + i / nbx_skip;
-    }
-  }
-  const int x0 = bx * B, y0 = by * B, h = B / 2, CW = B / 4;
-  const int bw = min(B, width - x0), bh = min(B, height - y0);
-  ref += (size_t)f * ref_frame_stride;
-  cur += (size_t)f * cur_frame_stride;
-
-  for (int i = tid; i < B * CW; i += GEN_THREADS) {
-    const int y = i / CW, xw = (i % CW) * 4;
-    uint32_t w = 0;
-    for (int e = 0; e < 4; e++)
-      if (y < bh && xw + e < bw) w |= (uint32_t)cur[(size_t)(y0 + y) * stride + x0 + xw + e] << (8 * e);
-    cblk[i] = w;
-  }
-  __syncthreads();
-
-  const int cx0 = max(0, x0 - S), cx1 = min(width, x0 + bw + S) - bw;
-  const int cy0 = max(0, y0 - S), cy1 = min(height, y0 + bh + S) - bh;
-  const int ncx = cx1 - cx0 + 1, ncand = ncx * (cy1 - cy0 + 1);
-  uint64_t best[P_N];
-#pragma unroll
-  for (int p = 0; p < P_N; p++) best[p] = ~0ull;
-  for (int t = tid; t < ncand; t += GEN_THREADS) {
-    const int cy = cy0 + t / ncx, cx = cx0 + t % ncx;
-    uint32_t q[4] = {0, 0, 0, 0};  // TL, TR, BL, BR
-    for (int y = 0; y < bh; y++) {
-      const uint8_t* r = ref + (size_t)(cy + y) * stride + cx;
-      for (int k = 0; k < CW; k++) {
-        const int xw = 4 * k;
-        if (xw >= bw) break;
-        uint32_t w = 0;
-        for (int e = 0; e < 4; e++)
-          if (xw + e < bw) w |= (uint32_t)r[xw + e] << (8 * e);
-        const int qi = (y >= h ? 2 : 0) + (xw >= h ? 1 : 0);  // (h is a multiple of 4)
-        q[qi] = __builtin_amdgcn_sad_u8(w, cblk[y * CW + k], q[qi]);
-      }
-    }
-    const int dx = cx - x0, dy = cy - y0;
-    const uint32_t c9[P_N] = {q[0] + q[1] + q[2] + q[3], q[0] + q[1], q[2] + q[3], q[0] + q[2],
-                              q[1] + q[3], q[0], q[1], q[2], q[3]};
-#pragma unroll
-    for (int p = 0; p < P_N; p++) {
-      const uint64_t key = make_key(c9[p], dx, dy);
-      best[p] = key < best[p] ? key : best[p];
-    }
-  }
+// Records and mode of macroblock (bx, by) of frame f from its nine keys
+// (make_key / store_mv of me_kernels.h).
+__device__ __forceinline__ void part_store(const PartOut& o, int f, int bx, int by,
+                                           const uint64_t* k) {
+  const PartCells c = part_cells(o, f, bx, by);
+  int16_t* const mv[4] = {o.f.mv_2nx2n, o.f.mv_2nxn, o.f.mv_nx2n, o.f.mv_nxn};
+  uint32_t* const cost[4] = {o.f.cost_2nx2n, o.f.cost_2nxn, o.f.cost_nx2n, o.f.cost_nxn};
+  uint32_t j[P_N];
 #pragma unroll
   for (int p = 0; p < P_N; p++) {
-    uint64_t v = best[p];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const uint64_t u = __shfl_xor(v, off, 64);
-      v = u < v ? u : v;
+    j[p] = 0;
+    if (c.there[p]) {
+      j[p] = (uint32_t)(k[p] >> 32);
+      store_mv(mv[grid_of(p)] + 2 * c.at[p], 0, k[p]);
+      if (cost[grid_of(p)]) cost[grid_of(p)][c.at[p]] = j[p];
     }
-    if ((tid & 63) == 0) red[tid >> 6][p] = v;
   }
-  __syncthreads();
-  if (tid == 0) {
-    uint64_t k[P_N];
+  part_mode(o.f, c.at[P_FULL], j, o.lambda, 2, 4);
+}
+
+// ... with the rate: R from each winning displacement and the macroblock's
+// predictor (px, py), J in cost and J - lambda R in dist.
+__device__ __forceinline__ void part_rd_store(const PartRdOut& o, int f, int bx, int by,
+                                              const uint64_t* k, int px, int py) {
+  const PartCells c = part_cells(o, f, bx, by);
+  const me_part_rd_fields& F = o.f;
+  int16_t* const mv[4] = {F.f.mv_2nx2n, F.f.mv_2nxn, F.f.mv_nx2n, F.f.mv_nxn};
+  uint32_t* const cost[4] = {F.f.cost_2nx2n, F.f.cost_2nxn, F.f.cost_nx2n, F.f.cost_nxn};
+  uint32_t* const dist[4] = {F.dist_2nx2n, F.dist_2nxn, F.dist_nx2n, F.dist_nxn};
+  uint8_t* const bits[4] = {F.bits_2nx2n, F.bits_2nxn, F.bits_nx2n, F.bits_nxn};
+  uint32_t j[P_N];
 #pragma unroll
-    for (int p = 0; p < P_N; p++) {
-      uint64_t v = red[0][p];
-#pragma unroll
-      for (int w = 1; w < GEN_THREADS / 64; w++) v = red[w][p] < v ? red[w][p] : v;
-      k[p] = v;
+  for (int p = 0; p < P_N; p++) {
+    j[p] = 0;
+    if (c.there[p]) {
+      const int g = grid_of(p);
+      const int dx = (int)(k[p] & 0xFFFF) - 32768, dy = (int)((k[p] >> 16) & 0xFFFF) - 32768;
+      const uint32_t r = (uint32_t)(rd_bits(4 * dx - px) + rd_bits(4 * dy - py));
+      j[p] = (uint32_t)(k[p] >> 32);
+      store_mv(mv[g] + 2 * c.at[p], 0, k[p]);
+      if (cost[g]) cost[g][c.at[p]] = j[p];
+      if (dist[g]) dist[g][c.at[p]] = j[p] - o.lambda * r;
+      if (bits[g]) bits[g][c.at[p]] = (uint8_t)r;
     }
-    part_store(o, f, bx, by, k);
   }
+  part_mode(F.f, c.at[P_FULL], j, o.lambda, 3, 5);
 }
 
 // --------------------------------------------------------------------- fast
@@ -195,20 +174,7 @@ __device__ __forceinline__ void part_lane_keys(const uint64_t (&acc)[K][4], uint
 #pragma unroll
   for (int j = 0; j < K; j++) {
     uint32_t lo[P_N], hi[P_N];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      lo[P_TL + q] = (uint32_t)acc[j][q];
-      hi[P_TL + q] = (uint32_t)(acc[j][q] >> 32);
-    }
-    auto sum = [&](int d, int a, int b) {
-      lo[d] = pk_add(lo[a], lo[b]);
-      hi[d] = pk_add(hi[a], hi[b]);
-    };
-    sum(P_TOP, P_TL, P_TR);
-    sum(P_BOT, P_BL, P_BR);
-    sum(P_LEFT, P_TL, P_BL);
-    sum(P_RIGHT, P_TR, P_BR);
-    sum(P_FULL, P_TOP, P_BOT);
+    nine_sums(acc[j], lo, hi);
     const bool jv = j >= jlo && j <= jhi;
 #pragma unroll
     for (int p = 0; p < P_N; p++) {
@@ -226,25 +192,25 @@ __device__ __forceinline__ void part_lane_keys(const uint64_t (&acc)[K][4], uint
   }
 }
 
-// Workgroup (blockIdx.x, blockIdx.y, blockIdx.z) = (tile of PART_TB full-size
-// macroblocks, macroblock row, frame).  Dynamic LDS: the window (rows x pitch,
-// frame rows y0 - S .., columns X0 .., X0 = tile x - S - a a multiple of 4;
-// zeros outside the plane's bytes, whatever the neighbouring rows hold beyond
-// the frame's sides -- those candidates are masked), the tile's current blocks
-// (256 bytes each), then the 9 keys per macroblock.
+// Dynamic LDS: FastTile's, with 9 keys per macroblock.  This kernel keeps its
+// geometry, staging, task decode and block load written out (they say what
+// fast_tile, fast_stage, fast_task and load_block of me_tile_search.h say):
+// built from those it measured 0.4 % slower at 4K +-64, twice, with a
+// lane-task's listing all but equal to this one's (profiles/README.md).  It
+// shares the row walk, nine_sums, merge_key and the record writer.
 template <int K>
-__global__ __launch_bounds__(PART_FAST_THREADS) void me_part_fast_kernel(
+__global__ __launch_bounds__(TILE_THREADS) void me_part_fast_kernel(
     const uint8_t* __restrict__ ref, size_t ref_frame_stride, const uint8_t* __restrict__ cur,
     size_t cur_frame_stride, int width, int height, int stride, int S, int nbx_full, PartOut o) {
   extern __shared__ __align__(16) uint8_t smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  constexpr int NW = PART_FAST_THREADS / 64;
-  const int bx0 = (int)blockIdx.x * PART_TB, by = blockIdx.y, f = blockIdx.z;
-  const int nb = min(PART_TB, nbx_full - bx0);
-  const int G = partition_fast_groups(S), pitch = partition_fast_pitch(S);
+  constexpr int NW = TILE_THREADS / 64;
+  const int bx0 = (int)blockIdx.x * TILE_TB, by = blockIdx.y, f = blockIdx.z;
+  const int nb = min(TILE_TB, nbx_full - bx0);
+  const int G = tile_groups(S), pitch = tile_pitch(S);
   const int chunks = (2 * S + 1 + K - 1) / K, rows = chunks * K + 15;
   uint8_t* const cur_lds = smem + ((rows * pitch + 15) & ~15);
-  uint64_t* const keys = reinterpret_cast<uint64_t*>(cur_lds + PART_TB * 256);
+  uint64_t* const keys = reinterpret_cast<uint64_t*>(cur_lds + TILE_TB * 256);
   const int y0 = by * 16;
   const int a = ((bx0 * 16 - S) % 4 + 4) % 4;
   const int X0 = bx0 * 16 - S - a;
@@ -273,7 +239,7 @@ __global__ __launch_bounds__(PART_FAST_THREADS) void me_part_fast_kernel(
         rcur, (__attribute__((address_space(3))) void*)(cur_lds + b * 256), 4,
         (uint32_t)((y0 + y) * stride + (bx0 + b) * 16 + xw), 0, 0, 0);
   }
-  if (tid < PART_TB * P_N) keys[tid] = ~0ull;
+  if (tid < TILE_TB * P_N) keys[tid] = ~0ull;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -283,7 +249,7 @@ __global__ __launch_bounds__(PART_FAST_THREADS) void me_part_fast_kernel(
   const int lc0 = (dymin + S) / K, lc1 = (dymax + S) / K + 1;
   const int per_chunk = nb * G, T = (lc1 - lc0) * per_chunk;
   const uint32_t lds0 = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const uint8_t*)smem);
-  for (int t = tid; t < T; t += PART_FAST_THREADS) {
+  for (int t = tid; t < T; t += TILE_THREADS) {
     const int lcr = t / per_chunk, rem = t - lcr * per_chunk;
     const int b = rem / G, gi = rem - b * G;
     const int d0 = (lc0 + lcr) * K;  // first dy row of the task, as dy + S
@@ -295,7 +261,7 @@ __global__ __launch_bounds__(PART_FAST_THREADS) void me_part_fast_kernel(
       c[y][0] = v.x, c[y][1] = v.y, c[y][2] = v.z, c[y][3] = v.w;
     }
     uint64_t acc[K][4];
-    part_lane<K>(lds0 + (uint32_t)(d0 * pitch + 4 * (b * 4 + gi)), pitch, c, acc);
+    tile_lane<K, 4>(lds0 + (uint32_t)(d0 * pitch + 4 * (b * 4 + gi)), pitch, c, acc);
 
     const int dxmin = max(-S, -x0), dxmax = min(S, width - 16 - x0);
     const int jlo = dymin + S - d0, jhi = dymax + S - d0;
@@ -320,15 +286,95 @@ __global__ __launch_bounds__(PART_FAST_THREADS) void me_part_fast_kernel(
       if (best[p] < 0xFFFF0000u) {
         const int idx = (int)(best[p] & 0xFFFFu);
         const uint64_t key = make_key(best[p] >> 16, dxg + (idx & 3), d0 + (idx >> 2) - S);
-        // most lanes lose to a key already there: read before the atomic
-        if (key < keys[b * P_N + p])
-          atomicMin(reinterpret_cast<unsigned long long*>(&keys[b * P_N + p]),
-                    (unsigned long long)key);
+        merge_key(&keys[b * P_N + p], key);
       }
     }
   }
   __syncthreads();
   if (tid < nb) part_store(o, f, bx0 + tid, by, keys + tid * P_N);
+}
+
+// Every lane key of a valid rate-constrained candidate is below this one
+// (J < 2^26 - 1).
+constexpr uint32_t LANE_KEY_INVALID = 0xFFFFFFC0u;
+
+// The lane's nine 32-bit keys J << 6 | 4 j + i, ordered like (J, dy, dx) within
+// the lane.  rx[i] = lambda bits(4 dx_i - px) and ry[j] = lambda bits(4 dy_j -
+// py) come from the workgroup's rate tables, ~0 for a column or row outside
+// the macroblock's candidates: r = rx + ry saturates to ~0 there, and so does
+// every J = sad + r, whose key is then at least LANE_KEY_INVALID.  A valid J is
+// below 2^26 - 1 (65,280 + 66 lambda, lambda <= ME_RD_FAST_MAX_LAMBDA), so the
+// shift loses nothing.
+template <int K>
+__device__ __forceinline__ void part_rd_lane_keys(const uint64_t (&acc)[K][4],
+                                                  const uint32_t (&rx)[4], const uint32_t* ry,
+                                                  uint32_t (&best)[P_N]) {
+#pragma unroll
+  for (int p = 0; p < P_N; p++) best[p] = ~0u;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    uint32_t lo[P_N], hi[P_N];
+    nine_sums(acc[j], lo, hi);
+    const uint32_t rj = ry[j];
+    const uint32_t r0 = add_sat(rx[0], rj), r1 = add_sat(rx[1], rj);
+    const uint32_t r2 = add_sat(rx[2], rj), r3 = add_sat(rx[3], rj);
+#pragma unroll
+    for (int p = 0; p < P_N; p++) {
+      const uint32_t k0 = (add_sat(lo[p] & 0xFFFFu, r0) << 6) | (uint32_t)(4 * j);
+      const uint32_t k1 = (add_sat(lo[p] >> 16, r1) << 6) | (uint32_t)(4 * j + 1);
+      const uint32_t k2 = (add_sat(hi[p] & 0xFFFFu, r2) << 6) | (uint32_t)(4 * j + 2);
+      const uint32_t k3 = (add_sat(hi[p] >> 16, r3) << 6) | (uint32_t)(4 * j + 3);
+      best[p] = min(min(best[p], k0), min(k1, min(k2, k3)));
+    }
+  }
+}
+
+// Dynamic LDS: FastTile's, with 9 keys per macroblock, then the rate tables
+// without index bits (fill_rate_x / fill_rate_y).
+template <int K>
+__global__ __launch_bounds__(TILE_THREADS) void me_part_rd_fast_kernel(
+    const uint8_t* __restrict__ ref, size_t ref_frame_stride, const uint8_t* __restrict__ cur,
+    size_t cur_frame_stride, int width, int height, int stride, int S, int nbx_full,
+    PartRdOut o) {
+  extern __shared__ __align__(16) uint8_t smem[];
+  const int tid = threadIdx.x;
+  const FastTile t = fast_tile<K>(smem, S, nbx_full, height);
+  uint32_t* const rxt = reinterpret_cast<uint32_t*>(t.keys + TILE_TB * P_N);
+  uint32_t* const ryt = rxt + TILE_TB * 4 * t.G;
+  const size_t mb0 = (size_t)t.f * o.nbx * o.nby + (size_t)t.by * o.nbx + t.bx0;
+
+  fast_stage(t, smem, ref, ref_frame_stride, cur, cur_frame_stride, width, height, stride, S);
+  if (tid < TILE_TB * P_N) t.keys[tid] = ~0ull;
+  fill_rate_x<false>(rxt, t, S, width, o.pred, mb0, o.lambda);
+  fill_rate_y<K, false>(ryt, t, S, o.pred, mb0, o.lambda);
+  fast_stage_wait();
+
+  const int T = fast_tasks(t);
+  for (int i = tid; i < T; i += TILE_THREADS) {
+    const FastTask k = fast_task<K>(t, i);
+    uint32_t c[16][4];
+    load_block(t.cur_lds, k.b, c);
+    uint64_t acc[K][4];
+    tile_lane<K, 4>(fast_task_at(smem, t, k), t.pitch, c, acc);
+
+    const int dxg = 4 * k.gi - S - t.a;  // dx of the lane's first candidate
+    const uint4 rv = reinterpret_cast<const uint4*>(rxt)[k.b * t.G + k.gi];
+    const uint32_t rx[4] = {rv.x, rv.y, rv.z, rv.w};
+    uint32_t best[P_N];
+    part_rd_lane_keys<K>(acc, rx, ryt + k.b * t.chunks * K + k.d0, best);
+#pragma unroll
+    for (int p = 0; p < P_N; p++) {
+      if (best[p] < LANE_KEY_INVALID) {
+        const int idx = (int)(best[p] & 63u);
+        merge_key(&t.keys[k.b * P_N + p],
+                  make_key(best[p] >> 6, dxg + (idx & 3), k.d0 + (idx >> 2) - S));
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < t.nb)
+    part_rd_store(o, t.f, t.bx0 + tid, t.by, t.keys + tid * P_N, pred_at(o.pred, mb0 + tid, 0),
+                  pred_at(o.pred, mb0 + tid, 1));
 }
 
 // One thread per cell of the NxN grid (blockIdx.y: the frame).
@@ -359,28 +405,20 @@ PartOut part_out(const me_part_fields& f, int width, int height, int blk, uint32
 
 hipError_t launch_partition_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,
                                    const me_part_fields& out, hipStream_t stream) {
-  const PartOut o = part_out(out, b.width, b.height, b.blk, lambda);
-  const int nbx_full = b.width / b.blk, nby_full = b.height / b.blk;
-  if (fast) {
-    const int rows = partition_fast_rows(range), pitch = partition_fast_pitch(range);
-    const size_t lds = (size_t)((rows * pitch + 15) & ~15) + PART_TB * 256 + PART_TB * P_N * 8;
-    const dim3 grid((unsigned)((nbx_full + PART_TB - 1) / PART_TB), (unsigned)nby_full,
-                    (unsigned)b.n_frames);
-    hipLaunchKernelGGL(me_part_fast_kernel<PART_K>, grid, dim3(PART_FAST_THREADS), lds, stream, b.ref,
-                       b.ref_frame_stride, b.cur, b.cur_frame_stride, b.width, b.height, b.stride, range,
-                       nbx_full, o);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  // every macroblock, or the rim the fast kernel left: (nbx - nbx_full) right
-  // columns of all rows, then nbx_full macroblocks of each clipped bottom row
-  const int sx = fast ? nbx_full : 0, sy = fast ? nby_full : 0;
-  const int n = fast ? (o.nbx - sx) * o.nby + sx * (o.nby - sy) : o.nbx * o.nby;
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(me_part_generic_kernel, dim3((unsigned)n, (unsigned)b.n_frames),
-                     dim3(GEN_THREADS), 0, stream, b.ref, b.ref_frame_stride, b.cur, b.cur_frame_stride,
-                     b.width, b.height, b.stride, b.blk, range, sx, sy, o);
-  return hipGetLastError();
+  return launch_tile_search<PartOut>(b, range, fast, me_part_fast_kernel<PART_K>,
+                                     tile_lds_bytes(range, PART_K, P_N, false),
+                                     me_tile_generic_kernel<4, false, PartOut, part_store>,
+                                     part_out(out, b.width, b.height, b.blk, lambda), stream);
+}
+
+hipError_t launch_partition_rd_search(const FrameBatch& b, int range, uint32_t lambda, bool fast,
+                                      const int16_t* pred, const me_part_rd_fields& out,
+                                      hipStream_t stream) {
+  const PartOut g = part_out(out.f, b.width, b.height, b.blk, lambda);
+  return launch_tile_search<PartRdOut>(b, range, fast, me_part_rd_fast_kernel<PART_RD_K>,
+                                       tile_lds_bytes(range, PART_RD_K, P_N, true),
+                                       me_tile_generic_kernel<4, true, PartRdOut, part_rd_store>,
+                                       PartRdOut{out, pred, g.nbx, g.nby, g.nhx, g.nhy, lambda}, stream);
 }
 
 hipError_t launch_partition_leaf(int width, int height, int blk, int n_frames,

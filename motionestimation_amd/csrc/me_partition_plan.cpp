@@ -13,16 +13,13 @@ me_status partition_check(int width, int height, int stride, int blk, int range,
                           const char** why) {
   const char* dummy;
   if (!why) why = &dummy;
-  if (width <= 0 || height <= 0) return *why = "frame size", ME_EINVAL;
-  if (stride < width) return *why = "stride below width", ME_EINVAL;
-  if (range < 0) return *why = "negative search_range", ME_EINVAL;
+  if (const me_status s = frame_check(width, height, stride, why)) return s;
+  if (range < 0) return *why = NEGATIVE_RANGE, ME_EINVAL;
   if (blk != 8 && blk != 16 && blk != 32)
     return *why = "partition search takes block_size 8, 16 or 32", ME_EUNSUPPORTED;
   if (range > ME_PART_MAX_RANGE)
     return *why = "partition search_range above ME_PART_MAX_RANGE", ME_EUNSUPPORTED;
-  if ((long long)stride * height >= (1LL << 31))
-    return *why = "plane of 2 GiB or more", ME_EUNSUPPORTED;
-  return ME_OK;
+  return plane_check(stride, height, why);
 }
 
 }  // namespace me
@@ -44,12 +41,8 @@ me_status me_partition_counts(int width, int height, int blk, int counts[4]) {
 
 int me_partition_kernel_variant(int width, int height, int stride, int blk, int range) {
   if (me::partition_check(width, height, stride, blk, range, nullptr) != ME_OK) return -1;
-  // The fast kernel stages its window with 4-byte LDS DMA granules (none may
-  // straddle a row's end: width and pitch multiples of 4) and holds a 16 x 16
-  // block's quadrant SADs in packed u16.
-  const bool fast = blk == 16 && range <= me::PART_FAST_MAX_RANGE && width % 4 == 0 &&
-                    stride % 4 == 0 && width >= 16 && height >= 16;
-  return fast ? ME_PART_KERNEL_FAST : ME_PART_KERNEL_GENERIC;
+  return me::tile_fast_shape(width, height, stride, blk, range) ? ME_PART_KERNEL_FAST
+                                                                : ME_PART_KERNEL_GENERIC;
 }
 
 int me_partition_rd_kernel_variant(int width, int height, int stride, int blk, int range,

@@ -13,16 +13,13 @@ me_status rd_check(int width, int height, int stride, int blk, int range, uint32
                    const char** why) {
   const char* dummy;
   if (!why) why = &dummy;
-  if (width <= 0 || height <= 0) return *why = "frame size", ME_EINVAL;
-  if (stride < width) return *why = "stride below width", ME_EINVAL;
+  if (const me_status s = frame_check(width, height, stride, why)) return s;
   if (blk < 1 || blk > ME_MAX_BLOCK) return *why = "block_size", ME_EINVAL;
-  if (range < 0) return *why = "negative search_range", ME_EINVAL;
+  if (range < 0) return *why = NEGATIVE_RANGE, ME_EINVAL;
   if (lambda > ME_RD_MAX_LAMBDA) return *why = "lambda above ME_RD_MAX_LAMBDA", ME_EINVAL;
   if (range > ME_RD_MAX_RANGE)
     return *why = "rate-constrained search_range above ME_RD_MAX_RANGE", ME_EUNSUPPORTED;
-  if ((long long)stride * height >= (1LL << 31))
-    return *why = "plane of 2 GiB or more", ME_EUNSUPPORTED;
-  return ME_OK;
+  return plane_check(stride, height, why);
 }
 
 }  // namespace me
@@ -37,11 +34,8 @@ int me_mv_bits(int v) {
 
 int me_rd_kernel_variant(int width, int height, int stride, int blk, int range, uint32_t lambda) {
   if (me::rd_check(width, height, stride, blk, range, lambda, nullptr) != ME_OK) return -1;
-  // The fast kernel stages its window with 4-byte LDS DMA granules (none may
-  // straddle a row's end: width and pitch multiples of 4), holds a 16 x 16
-  // block's SADs in packed u16 and a candidate's J in 26 bits of a 32-bit key.
-  const bool fast = blk == 16 && range <= me::RD_FAST_MAX_RANGE && width % 4 == 0 &&
-                    stride % 4 == 0 && width >= 16 && height >= 16 &&
+  // The fast kernel holds a candidate's J in 26 bits of a 32-bit key.
+  const bool fast = me::tile_fast_shape(width, height, stride, blk, range) &&
                     lambda <= ME_RD_FAST_MAX_LAMBDA;
   return fast ? ME_RD_KERNEL_FAST : ME_RD_KERNEL_GENERIC;
 }

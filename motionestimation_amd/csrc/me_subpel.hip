@@ -34,7 +34,7 @@
 
 #include "me.h"
 #include "me_kernels.h"
-#include "me_partition_lane.h"
+#include "me_tile_search.h"
 #include "me_rd.h"
 
 namespace me {
@@ -790,7 +790,7 @@ __global__ __launch_bounds__(QpelGeom<TB>::NT) void me_bipred_compensate_kernel(
 // quarter-pel refinement"; DESIGN.md has the layout and the counts) ----
 //
 // One workgroup per macroblock refines its nine partitions (P_FULL .. P_BR of
-// me_partition_lane.h's order: the macroblock, top, bottom, left, right, and
+// me_tile_search.h's order: the macroblock, top, bottom, left, right, and
 // the quarters TL, TR, BL, BR).  The lanes keep qpel_pixels' layout of the
 // whole macroblock, one 4-pixel group each (GPL = 1 for B in {8, 16, 32}); a
 // group lies in exactly one quarter, so a candidate is costed once per lane
